@@ -32,7 +32,10 @@ N = 1 line carries that one-GPU leg too (`strong_base` = config 4 at 1 of 8 GPUs
 either mode at any N.
 
 After the timed region (never inside it) the step CHECKS ITSELF: frames and per-pose losses of the first and last
-pose against the scalar C oracle (`verified`); a mismatch makes the process exit non-zero.
+pose against the scalar C oracle (`verified`); a mismatch makes the process exit non-zero.  `--dump-outputs DIR` also
+writes what the last timed step computed (rank 0's frame, the per-pose losses, the volume / source / direction
+gradients) as DIR/<name>.npy, larger arrays as a fixed seeded sample (dump_outputs); the inputs are analytic, so two
+builds run with the same arguments can be compared output for output.
 
 Inputs (volume -- canonical and its converted copy --, poses) are resident in HBM
 before the timed region.  The step (diffus_amd.CapturedStep) is issued either eagerly (two C-ABI calls, three kernels)
@@ -147,8 +150,14 @@ def parse_args(argv=None):
                     help="skip the after-the-timed-loop comparison of the step's frames and losses with the CPU oracle")
     ap.add_argument("--no-scaling-legs", action="store_true",
                     help="skip the extra timed legs (one-GPU base of the strong curve, weak figure, bucketed gather)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (rank 0's frame, the per-pose losses "
+                         "and the gradients) as DIR/<name>.npy, at most 60 MB in all (see dump_outputs)")
     ap.add_argument("--fail-rank", type=int, default=-1, help=argparse.SUPPRESS)   # tests: this rank exits 3 before the rendezvous
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -1075,6 +1084,32 @@ def verify_step(args, vol_of_pose, src_all, dirs_all, local_lo, hp, losses_all, 
             "max_rel_err": max([x["rel_err"] for x in frames + losses] or [0.0]), "ok": bool(ok)}
 
 
+DUMP_BYTES = 60 * 10**6          # all .npy files of one --dump-outputs together, headers included
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES):
+    """Write `arrays` (name -> float32/float64 tensor) as out_dir/<name>.npy, so that two builds can be compared output for
+    output.  The smallest arrays are written whole; an array larger than an even share of the bytes still left becomes its
+    values at a fixed sample of flat indices (seed 0, increasing order): the same positions in every run with the same
+    shapes.  -> {name: {"shape", "dtype", "sampled"}} (sampled: number of values kept, or None for the whole array)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel() * kv[1].element_size())
+    left = budget - 128 * len(items)                      # room for the .npy headers
+    info = {}
+    for i, (name, t) in enumerate(items):
+        a = t.detach().cpu().numpy()
+        keep = min(a.size, left // (len(items) - i) // a.itemsize)
+        sampled = None
+        if keep < a.size:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a, sampled = a.reshape(-1)[idx], int(keep)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+        info[name] = {"shape": list(t.shape), "dtype": str(a.dtype), "sampled": sampled}
+    return info
+
+
 def worker(args):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -1145,6 +1180,13 @@ def worker(args):
     value = ray_steps * args.steps / dt
     if dist is not None:      # every rank must hold all P losses, in pose order, and they must be finite
         assert torch.isfinite(run.losses_all).all() and float(run.losses_all.abs().min()) > 0, "loss gather failed"
+    # what the last timed step handed its caller, before anything below runs the step's buffers again
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        outs = {"frame": hp.frame, "loss": run.losses_all, "grad_sources": hp.gsrc, "grad_directions": hp.gdirs}
+        if hp.gvol is not None:
+            outs["grad_volume"] = hp.gvol
+        dumped = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, outs)}
 
     # --- the step checks itself (outside the timed region): rank 0's first and last pose as frames, and the gathered
     # losses of those two plus the LAST pose of the whole job (the last rank's, so the gather's pose order is covered) ---
@@ -1374,6 +1416,7 @@ def worker(args):
                                                           else "torch.distributed.all_gather_into_tensor"),
             },
             "verified": verified,
+            "dumped_outputs": dumped,
             "roofline": {
                 # measured first: `achieved` / `frac` are the HBM-side bytes of the committed PMC passes over the
                 # live launch time; the contract's no-reuse ALGORITHMIC figure sits beside them under `algorithmic`

@@ -214,3 +214,56 @@ def test_gpu_numa_cpus_from_sysfs(tmp_path):
     assert bench.gpu_numa_cpus(3, {}, **kw) is None                     # no such GPU
     assert bench.gpu_numa_cpus(0, {"HIP_VISIBLE_DEVICES": "1,0"}, **kw) is None
     assert bench.gpu_numa_cpus(0, {}, kfd_nodes=str(tmp_path / "missing"), drm=str(drm), numa=str(numa)) is None
+
+
+def test_dump_outputs_keeps_small_arrays_whole_and_samples_large_ones_the_same_way(tmp_path):
+    """bench.dump_outputs: every array as <name>.npy within the byte budget; the small ones whole, the one that does not fit
+    as its values at a fixed set of increasing flat indices, the same set on every call."""
+    import numpy as np
+    import torch
+    import bench
+    arrays = {"loss": torch.arange(4, dtype=torch.float32), "grad": torch.arange(60, dtype=torch.float64).reshape(3, 20),
+              "big": torch.arange(2000, dtype=torch.float32).reshape(20, 100)}
+    budget = 128 * 3 + 4 * 4 + 8 * 60 + 4 * 500
+    info = bench.dump_outputs(str(tmp_path / "a"), arrays, budget=budget)
+    bench.dump_outputs(str(tmp_path / "b"), arrays, budget=budget)
+    assert sorted(os.listdir(tmp_path / "a")) == ["big.npy", "grad.npy", "loss.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= budget
+    for name in ("loss", "grad"):
+        a = np.load(tmp_path / "a" / f"{name}.npy")
+        assert info[name]["sampled"] is None and a.dtype == arrays[name].numpy().dtype
+        np.testing.assert_array_equal(a, arrays[name].numpy())
+    big = np.load(tmp_path / "a" / "big.npy")
+    assert info["big"] == {"shape": [20, 100], "dtype": "float32", "sampled": 500} and big.shape == (500,)
+    assert np.all(np.diff(big) > 0) and big[0] >= 0 and big[-1] < 2000        # values = their flat indices here
+    np.testing.assert_array_equal(big, np.load(tmp_path / "b" / "big.npy"))
+
+
+def test_steps_below_one_are_refused():
+    import bench
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_what_the_last_timed_step_computed(tmp_path):
+    """`bench.py --dump-outputs DIR` on a small workload: the frame, the per-pose losses (= sum of the frame's squares) and
+    the three gradients of the timed step, whole, and a result line that says K steps were timed."""
+    import numpy as np
+    out_dir = tmp_path / "dump"
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "7", "--warmup", "2", "--prewarm-ms", "0",
+                        "--n", "64", "--poses", "2", "--rays", "16", "--samples", "64", "--no-cpu-baseline", "--no-callers",
+                        "--no-scaling-legs", "--dump-outputs", str(out_dir)], env=_env(), capture_output=True, text=True,
+                       timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = _json_line(r.stdout)
+    assert out["steps"] == 7 and out["ms_per_step"] > 0 and out["verified"]["ok"]
+    shapes = {"frame": [2, 16, 64], "loss": [2], "grad_sources": [2, 3], "grad_directions": [2, 16, 3],
+              "grad_volume": [64, 64, 64]}
+    assert {k: v["shape"] for k, v in out["dumped_outputs"]["arrays"].items()} == shapes
+    got = {k: np.load(out_dir / f"{k}.npy") for k in shapes}
+    for k, shape in shapes.items():
+        assert list(got[k].shape) == shape and got[k].dtype == np.float32 and np.isfinite(got[k]).all(), k
+    want = (got["frame"].astype(np.float64) ** 2).sum(axis=(1, 2))
+    np.testing.assert_allclose(got["loss"], want, rtol=1e-4)
+    assert np.abs(got["grad_volume"]).max() > 0 and np.abs(got["grad_sources"]).max() > 0
