@@ -14,7 +14,7 @@ node with a single RCCL gather".  One process per GPU, `torch.distributed`
     learned is there a second collective: one all_reduce(SUM) of its gradient --
     of the PART of it a step can have touched (allreduce_box: the slice the
     reference's training loop learns, 256 KiB at 256^3; allreduce_touched: the
-    union of the bricks the ranks' scatters added into), not of all 64 MiB.
+    union of the bricks the ranks' scatters added into this step), not of all 64 MiB.
 """
 from __future__ import annotations
 
@@ -80,15 +80,18 @@ def allreduce_box(gvol: torch.Tensor, box, group=None, scratch: Optional[torch.T
 
 def allreduce_touched(gvol_bricked: torch.Tensor, touched: torch.Tensor, group=None) -> int:
     """Sum, in place, a shared volume's BRICKED gradient scratch over the ranks, moving only bricks some rank's scatter added
-    into: the touched-brick flags (one per 4 x 4 x 2 brick, set by the scatter kernel) are OR-ed over the ranks (all_reduce(MAX)
-    of one byte per brick: 512 KiB at 256^3), the union's bricks are packed, summed (one all_reduce) and written back, and every
-    rank's flags become the union -- so that each rank's diffus_gradbuf_flush hands back the same summed gradient.  Call it
-    between the scatter and the flush (CapturedStep.bwd(BWD_SCATTER) / finish_grad()).  Returns the bytes through the two
-    collectives.  A 32-pose step touches ~80 000 of the 524 288 bricks of a 256^3 volume: 10 MB instead of 64 MiB.
+    into: the LIVE touched-brick flags (flag 1, set by the scatter kernel; one per 4 x 4 x 2 brick) are OR-ed over the ranks
+    (all_reduce(MAX) of one byte per brick: 512 KiB at 256^3), the live union's bricks are packed, summed (one all_reduce) and
+    written back, and every rank's flag of a brick in the live union becomes 1 -- so that each rank's diffus_gradbuf_flush
+    hands back the same summed gradient.  Stale flags (2, left by a PERSISTENT flush: `out` holds the previous step's values,
+    the scratch is zero) stay per rank and move nothing: a brick stale on one rank and live on another is live everywhere
+    after the call, a brick stale on every rank keeps its 2, so each flush clears it in `out`.  Call it between the scatter
+    and the flush (CapturedStep.bwd(BWD_SCATTER) / finish_grad()).  Returns the bytes through the two collectives.  A 32-pose
+    step touches ~80 000 of the 524 288 bricks of a 256^3 volume: 10 MB instead of 64 MiB.
     (One host round trip for the size of the union: `nonzero`.)"""
     nb = touched.numel()
     bricks = gvol_bricked.view(nb, -1)
-    flags = (touched != 0).to(torch.uint8)
+    flags = (touched == 1).to(torch.uint8)                           # live scratch only: a stale brick (2) holds zeros
     dist.all_reduce(flags, op=dist.ReduceOp.MAX, group=group)        # (NCCL has no bitwise OR: a byte per brick, MAX)
     idx = flags.nonzero(as_tuple=True)[0]
     moved = flags.numel() * flags.element_size()
@@ -96,8 +99,9 @@ def allreduce_touched(gvol_bricked: torch.Tensor, touched: torch.Tensor, group=N
         packed = bricks.index_select(0, idx)
         dist.all_reduce(packed, op=dist.ReduceOp.SUM, group=group)
         bricks.index_copy_(0, idx, packed)
-        # a brick this rank did not touch itself: flag 1 (live scratch: the flush must convert it), as the scatter would have set
-        touched.masked_fill_((flags != 0) & (touched == 0), 1)
+        # a brick this rank did not touch itself (flag 0, or 2: stale here): flag 1 (live scratch: the flush must convert it),
+        # as the scatter would have set
+        touched.masked_fill_((flags != 0) & (touched != 1), 1)
         moved += packed.numel() * packed.element_size()
     return moved
 

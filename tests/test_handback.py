@@ -564,3 +564,49 @@ def test_a_graph_of_several_steps_leaves_what_one_step_leaves(Step):
     assert torch.all(many.gvol_k == 0)
     with pytest.raises(AttributeError):
         many.capture("no_such_stage")
+
+
+@pytest.mark.parametrize("d,shift", [((9, 10, 7), 0), ((33, 70, 130), 0), ((33, 70, 130), 1), ((40, 36, 129), 0)])
+def test_flush_call_sequences_equal_the_numpy_model(d, shift):
+    """diffus_gradbuf_flush over a sequence of calls on ONE buffer set -- a run of PERSISTENT calls, STORE on top of it,
+    PERSISTENT again, ACCUMULATE over the stale flags that leaves, DENSE -- against oracle/handback.flush, bitwise after
+    every call (`out`, scratch, flags).  Between calls the scatter is imitated: random bricks get values added into their
+    scratch and flag 1, the other flags stay as the last call left them.  The CPU tests of the multi-rank hand-back rely
+    on this model."""
+    from diffus_amd import _lib
+    from oracle import handback as hb
+    lib = _lib.load()
+    assert (hb.STORE, hb.ACCUMULATE, hb.PERSISTENT, hb.DENSE) == (_lib.FLUSH_STORE, _lib.FLUSH_ACCUMULATE,
+                                                                  _lib.FLUSH_PERSISTENT, _lib.FLUSH_DENSE)
+    nb = lib.diffus_brick_count(*d)
+    assert nb == hb.brick_count(d) and lib.diffus_bricked_floats(*d) == nb * 32
+    rng = np.random.default_rng(sum(d) + shift)
+    m_b = np.zeros(nb * 32, np.float32)
+    m_t = np.zeros(nb, np.int32)
+    m_o = rng.standard_normal(d).astype(np.float32)
+    bricked = torch.zeros(nb * 32, device="cuda")
+    touched = torch.zeros(nb, dtype=torch.int32, device="cuda")
+    store = torch.empty(int(np.prod(d)) + shift, device="cuda")
+    out = store[shift:].view(d)
+    out.copy_(torch.from_numpy(m_o))
+    seq = [hb.PERSISTENT] * 4 + [hb.STORE] + [hb.PERSISTENT] * 2 + [hb.ACCUMULATE, hb.PERSISTENT, hb.DENSE, hb.PERSISTENT]
+    seen_stale = 0
+    for i, mode in enumerate(seq):
+        pick = rng.random(nb) < (0.3, 0.1, 0.5)[i % 3]
+        vals = rng.standard_normal((nb, 32)).astype(np.float32)
+        idx = np.flatnonzero(pick)
+        m_b.reshape(nb, 32)[idx] += vals[idx]
+        m_t[idx] = 1
+        seen_stale += int((m_t == 2).sum())
+        gi = torch.from_numpy(idx).cuda()
+        bricked.view(nb, 32).index_add_(0, gi, torch.from_numpy(vals[idx]).cuda())
+        touched[gi] = 1
+        assert lib.diffus_gradbuf_flush(vp(bricked), vp(touched), *d, vp(out), mode, None) == 0
+        torch.cuda.synchronize()
+        hb.flush(m_b, m_t, m_o, mode)
+        got_o = out.cpu().numpy()
+        assert np.array_equal(got_o.view(np.uint32), m_o.view(np.uint32)), (i, mode, int((got_o != m_o).sum()))
+        assert np.array_equal(bricked.cpu().numpy().view(np.uint32), m_b.view(np.uint32)), (i, mode)
+        assert np.array_equal(touched.cpu().numpy(), m_t), (i, mode)
+        assert not np.any(m_b)                                            # the model itself: scratch all-zero again
+    assert seen_stale > 0                                                 # calls met flags of 2 left by the one before
