@@ -11,14 +11,14 @@ from .renderer import (BrickedVolume, UltrasoundRenderer, brick_volume, compute_
                        propagate_full_rays_batched,
                        pair_volume, render_poses, resolve_start, trace_rays, unbrick_volume)
 
-from .artifacts import apply_artifacts  # noqa: F401,E402
+from .artifacts import apply_artifacts, artifact_noise  # noqa: F401,E402
 from .splat import differentiable_splat, rotate_around_apex, splat_frames  # noqa: F401,E402
 from .impedance import ImpedanceEstimator, create_brain_mask, masked_stats, zscore_normalize  # noqa: F401,E402
 from .captured import CapturedStep  # noqa: F401,E402
 from .losses import ssim_loss  # noqa: F401,E402
 from .raster import rasterize_fan  # noqa: F401,E402
 
-__all__ = ["ssim_loss", "rasterize_fan", "prop_single_ray", "propagate_full_rays_batched", "custom_nearest_sampler", "CapturedStep", "ImpedanceEstimator", "create_brain_mask", "zscore_normalize", "masked_stats", "apply_artifacts", "compute_gaussian_pulse", "gaussian_pulse", "FanPose", "compute_us_apex_and_direction", "cone_us_to_mri_world", "voxel_to_world", "world_to_voxel", "mri_to_us_point", "us_to_mri_point", "rotation_from_rotvec",
+__all__ = ["ssim_loss", "rasterize_fan", "prop_single_ray", "propagate_full_rays_batched", "custom_nearest_sampler", "CapturedStep", "ImpedanceEstimator", "create_brain_mask", "zscore_normalize", "masked_stats", "apply_artifacts", "artifact_noise", "compute_gaussian_pulse", "gaussian_pulse", "FanPose", "compute_us_apex_and_direction", "cone_us_to_mri_world", "voxel_to_world", "world_to_voxel", "mri_to_us_point", "us_to_mri_point", "rotation_from_rotvec",
            "differentiable_splat", "rotate_around_apex", "splat_frames", "UltrasoundRenderer", "compute_echo_traces", "render_poses", "trace_rays", "resolve_start",
            "generate_cone_directions", "fan_directions", "fan_directions_torch", "DiffusError", "BrickedVolume", "brick_volume",
            "unbrick_volume", "pair_volume"]

@@ -16,7 +16,8 @@ EXPORTS = ("diffus_abi_version", "diffus_strerror", "diffus_workspace_bytes", "d
            "diffus_pair_volume", "diffus_convert_volume_box", "diffus_brick_count", "diffus_gradbuf_flush",
            "diffus_render_fwd", "diffus_render_bwd", "diffus_render_bwd_mse", "diffus_render_step_mse", "diffus_trace_rays", "diffus_echo_traces",
            "diffus_loss_sumsq", "diffus_splat_workspace_bytes", "diffus_splat_fwd", "diffus_splat_bwd",
-           "diffus_artifacts_workspace_bytes", "diffus_artifacts",
+           "diffus_artifacts_workspace_bytes", "diffus_artifacts", "diffus_artifacts_bwd_workspace_bytes",
+           "diffus_artifacts_bwd", "diffus_artifacts_noise",
            "diffus_mlp_fwd", "diffus_mlp_workspace_bytes", "diffus_mlp_bwd", "diffus_brain_mask_workspace_bytes",
            "diffus_brain_mask", "diffus_masked_stats_workspace_bytes", "diffus_masked_stats", "diffus_rows_conv1d",
            "diffus_prop_single_ray", "diffus_propagate_rays", "diffus_sample_points",
@@ -121,6 +122,12 @@ def load():
     lib.diffus_artifacts_workspace_bytes.argtypes = [i, i, i]
     lib.diffus_artifacts.restype = i
     lib.diffus_artifacts.argtypes = [vp, i, i, i, d, d, d, d, vp, vp, C.c_uint64, vp, vp, sz, vp]
+    lib.diffus_artifacts_bwd_workspace_bytes.restype = sz
+    lib.diffus_artifacts_bwd_workspace_bytes.argtypes = [i, i, i]
+    lib.diffus_artifacts_bwd.restype = i
+    lib.diffus_artifacts_bwd.argtypes = [vp, i, i, i, d, d, d, d, vp, vp, C.c_uint64, vp, vp, vp, sz, vp]
+    lib.diffus_artifacts_noise.restype = i
+    lib.diffus_artifacts_noise.argtypes = [i, i, i, d, d, C.c_uint64, vp, vp, vp]
     lib.diffus_mlp_fwd.restype = i
     lib.diffus_mlp_fwd.argtypes = [vp, vp, sz, vp, f, f, f, f, vp, sz, vp]
     lib.diffus_mlp_workspace_bytes.restype = sz

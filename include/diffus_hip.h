@@ -428,6 +428,33 @@ int diffus_artifacts(const float *frame, int P, int R, int N,
                      double *out, void *workspace, size_t workspace_bytes, diffus_stream_t stream);
 
 /*
+ * Backward of diffus_artifacts: the artifact chain of reference src/renderer.py:535-601 (sharpen_np :535-543,
+ * add_speckle_arcs_np :545-583, add_depth_dependent_lateral_blur_np :585-601, run by plot_beam_frame :264-273), whose
+ * NumPy/SciPy original has no gradient at all.  Same frame, parameters, noise / seed as the forward call;
+ * gout (P,R,N) float64 = d loss / d out; gframe (P,R,N) float64 (overwritten) = d loss / d frame.  The gradient is the
+ * one torch autograd gives for the chain restated in float64 torch ops: speckle `s[s < 0] = 0` passes nothing where
+ * frame * radial * local < 0; the lateral blur and the unsharp mask transpose their 'reflect' filters; the clip is
+ * torch.clamp(u, x.amin(), x.amax()) per frame, a bound's summed gradient shared evenly by the elements of x equal to
+ * it.  None for the noise, std_*, max_sigma or alpha.  Stages 1 and 2 are recomputed with the forward's own kernels (the
+ * noise drawn again from `seed` when not given).  Bitwise repeatable (fixed-order reductions).
+ */
+size_t diffus_artifacts_bwd_workspace_bytes(int P, int R, int N);
+int diffus_artifacts_bwd(const float *frame, int P, int R, int N,
+                         double std_radial, double std_local, double max_sigma, double alpha,
+                         const double *radial_noise, const double *local_noise, uint64_t seed,
+                         const double *gout, double *gframe,
+                         void *workspace, size_t workspace_bytes, diffus_stream_t stream);
+
+/*
+ * The speckle factors a seeded diffus_artifacts call multiplies by (the chain of reference src/renderer.py:535-601;
+ * add_speckle_arcs_np :545-583 draws N(1, std_radial (1 + depth^2)) per depth and N(1, std_local (1 + depth^1.5)) per
+ * sample), from the same Philox4x32-10 stream: radial_out (P,N), local_out (P,R,N) float64.  Handed back as
+ * radial_noise / local_noise they reproduce the seeded frame bit for bit.
+ */
+int diffus_artifacts_noise(int P, int R, int N, double std_radial, double std_local, uint64_t seed,
+                           double *radial_out, double *local_out, diffus_stream_t stream);
+
+/*
  * Utility, not a reference function: the energy loss the benchmarks and examples
  * optimise.  loss[p] = sum(frame[p,:]^2) over the n floats of pose p, and (if
  * gframe != NULL) gframe = d loss / d frame = 2 * frame, in one streaming pass, one launch.
