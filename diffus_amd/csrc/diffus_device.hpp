@@ -104,12 +104,6 @@ __device__ __forceinline__ Mat mat_scale(const Mat &m, int e)
 __device__ __forceinline__ int mat_renorm(Mat &m)
 {
     float mx = fmaxf(fmaxf(fabsf(m.a), fabsf(m.b)), fmaxf(fabsf(m.c), fabsf(m.d)));
-#ifdef DIFFUS_RENORM_LDEXP // rounds 1-3: v_frexp_exp_i32_f32 + four v_ldexp_f32, 4.25 issue cycles each (tools/valu_issue_bench.hip)
-    // v_frexp_exp_i32_f32 returns 0 for +-0, inf and NaN: no branch needed, ldexp(x, 0) is a no-op
-    int ex = __builtin_amdgcn_frexp_expf(mx);
-    m = mat_scale(m, -ex);
-    return ex;
-#else
     // The scale 2^-ex as a float, straight from mx's exponent field (two full-rate integer instructions), and four
     // full-rate multiplies: exact like ldexp (a power of two; the products stay normal: mx 2^-ex is in [0.5, 1)).
     // ex = biased exponent - 126 is frexp's exponent for every normal mx.  mx = 0 (an all-zero matrix) scales zeros by
@@ -119,7 +113,6 @@ __device__ __forceinline__ int mat_renorm(Mat &m)
     const float sc = __uint_as_float(0x7e800000u - e23);
     m.a *= sc; m.b *= sc; m.c *= sc; m.d *= sc;
     return (int)(e23 >> 23) - 126;
-#endif
 }
 
 // a * b with DX9 rules: 0 * anything (NaN and infinity included) = 0, an IEEE product otherwise.  One full-rate
@@ -956,9 +949,6 @@ __device__ __forceinline__ void gather_interleaved_z(const Args &A, int seg0, in
                 const unsigned y0 = part_y<LAYOUT>(A.G, b.i0), y1 = part_y<LAYOUT>(A.G, b.i1);
                 const unsigned z0 = part_z<LAYOUT>(c.i0);
                 if constexpr (LAYOUT == DIFFUS_PAIRED) { // TWO 16-byte loads: rows x0 and x1, each (y0, y1) x (z0, z1)
-#ifdef DIFFUS_ABLATE_LOADS // timing probe (tools/): the addresses are computed, nothing is loaded
-                    F4a8 q0{__uint_as_float(x0 + y0 + z0), 1.f, __uint_as_float(y1), 1.f}, q1{__uint_as_float(x1 + y0 + z0), 1.f, 1.f, 1.f};
-#else
                     // (Tried: skipping loads whose weight is 0 for all 64 lanes -- rays that have left the volume --
                     // behind wave-uniform branches, and fetching the second column by an exec-masked extra load
                     // instead of storing it twice: hipcc then waits for the loads at every branch merge, 19.9 -> 24.1
@@ -972,7 +962,6 @@ __device__ __forceinline__ void gather_interleaved_z(const Args &A, int seg0, in
                     const F4a8 q0 = ldb_f32x4(vol, mad_u24_s((unsigned)a.i0 >> 2, sxB_u, mad_u24_40((unsigned)a.i0 & 3u, yz)));
                     const F4a8 q1 = ldb_f32x4(vol, mad_u24_s((unsigned)a.i1 >> 2, sxB_u, mad_u24_40((unsigned)a.i1 & 3u, yz)));
                     (void)y1; (void)x0; (void)x1;
-#endif
                     raw[jj][0] = q0.x; raw[jj][1] = q0.y; raw[jj][2] = q0.z; raw[jj][3] = q0.w;
                     raw[jj][4] = q1.x; raw[jj][5] = q1.y; raw[jj][6] = q1.z; raw[jj][7] = q1.w;
                 } else if constexpr (LAYOUT == DIFFUS_CANONICAL) {
@@ -998,17 +987,10 @@ __device__ __forceinline__ void gather_interleaved_z(const Args &A, int seg0, in
                 } else {
                     const unsigned z1 = part_z<LAYOUT>(c.i1);
                     const unsigned c00 = x0 + y0, c01 = x0 + y1, c10 = x1 + y0, c11 = x1 + y1;
-#ifdef DIFFUS_ABLATE_LOADS
-                raw[jj][0] = __uint_as_float(c00 + z0); raw[jj][1] = __uint_as_float(c00 + z1);
-                raw[jj][2] = __uint_as_float(c01 + z0); raw[jj][3] = __uint_as_float(c01 + z1);
-                raw[jj][4] = __uint_as_float(c10 + z0); raw[jj][5] = __uint_as_float(c10 + z1);
-                raw[jj][6] = __uint_as_float(c11 + z0); raw[jj][7] = __uint_as_float(c11 + z1);
-#else
                 raw[jj][0] = ldb_f32(vol, c00 + z0); raw[jj][1] = ldb_f32(vol, c00 + z1);
                 raw[jj][2] = ldb_f32(vol, c01 + z0); raw[jj][3] = ldb_f32(vol, c01 + z1);
                 raw[jj][4] = ldb_f32(vol, c10 + z0); raw[jj][5] = ldb_f32(vol, c10 + z1);
                 raw[jj][6] = ldb_f32(vol, c11 + z0); raw[jj][7] = ldb_f32(vol, c11 + z1);
-#endif
                 }
                 ta[jj] = a.t; tb[jj] = b.t; tc[jj] = c.t;
                 if (GRAD) { // the low-side tests, as lane masks (SGPR pairs: they cost no VGPR)
@@ -1029,13 +1011,7 @@ __device__ __forceinline__ void gather_interleaved_z(const Args &A, int seg0, in
                 z[j] = raw[jj][0];
                 if (GRAD) g0[j] = g1[j] = g2[j] = 0.f;
             } else {
-#ifdef DIFFUS_ABLATE_LERP
-                TriSample sm;
-                sm.v = raw[jj][0] + raw[jj][1] + raw[jj][2] + raw[jj][3] + raw[jj][4] + raw[jj][5] + raw[jj][6] + raw[jj][7] + ta[jj] + tb[jj] + tc[jj];
-                sm.g0 = sm.g1 = sm.g2 = 0.f;
-#else
                 TriSample sm = tri_lerp<GRAD>(raw[jj], ta[jj], tb[jj], tc[jj], GRAD ? k0[jj] : true, GRAD ? k1[jj] : true, GRAD ? k2[jj] : true);
-#endif
                 z[j] = sm.v;
                 if (GRAD) {
                     g0[j] = sm.g0; g1[j] = sm.g1; g2[j] = sm.g2;
@@ -1097,7 +1073,8 @@ struct NoScanHook {
     __device__ __forceinline__ bool operator()(const Mat &, Mat &) const { return false; }
 };
 // after_scan(Lincl, carry): called once between the wave scan and the sweep with this lane's INCLUSIVE prefix; it may
-// return true and a matrix that precedes the whole wave (the SPLIT kernels exchange the first half's total there).
+// return true and a matrix that precedes the whole wave (an exchange between the two waves of one ray; no caller passes
+// one since the forward's two-wave form was removed, but dropping the parameter changes echo_traces_kernel<8>'s code).
 template <int C, bool FAST = false, typename Hook = NoScanHook>
 __device__ __forceinline__ void echo_chunk(const float (&r)[C], int lane, float (&e)[C], const Mat *carry_in = nullptr,
                                            int last = -1, Mat *carry_out = nullptr, Hook &&after_scan = Hook())

@@ -1,4 +1,4 @@
-// render_fwd.hip -- forward kernel (plot_beam_frame), the stage-wise kernels, and their C-ABI entry points
+// render_fwd.hip -- forward kernel (plot_beam_frame), the median, the stage-wise kernels, and their C-ABI entry points
 #include "diffus_host.hpp"
 
 namespace {
@@ -22,22 +22,17 @@ __device__ unsigned long long *g_fwd_stamps = nullptr;
 #endif
 // SEG = true: the launch covers one 1024-sample segment of a longer ray (carries in the workspace); only
 // instantiated for C = 16.  SEG = false compiles every carry path away.
-// SPLIT = 2: the two waves of a 128-thread block take the two halves of one ray (see render_bwd_kernel); the first
-// half hands its last impedance sample and its total transfer-matrix product to the second through LDS.
-template <int C, int SAMPLER, int LAYOUT, int WPB, int PM, bool SEG = false, int SPLIT = 1>
+template <int C, int SAMPLER, int LAYOUT, int WPB, int PM, bool SEG = false>
 __global__ __launch_bounds__(kWave *WPB, (C <= 8 ? DIFFUS_FWD_MIN_WAVES : 1)) void render_fwd_kernel(Args A)
 {
-    static_assert(SPLIT == 1 || (SPLIT == 2 && WPB == 2 && !SEG), "SPLIT: one ray per block of two waves");
-    __shared__ float s_c[5]; // SPLIT exchange: total product of the first half (4) + its last sample
     const float *const cin = SEG ? A.cin : nullptr;
     float *const cout = SEG ? A.cout : nullptr;
     __shared__ __attribute__((aligned(16))) float lds[WPB][kWave * C];
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); // wave-uniform: ray-derived addresses stay scalar
-    const int part = (SPLIT > 1) ? wib : 0;
-    const long w = (SPLIT > 1) ? (long)xcd_remap(blockIdx.x, gridDim.x) : (long)xcd_remap(blockIdx.x, gridDim.x) * WPB + wib;
-    if (w >= (long)A.P * A.R) return; // wave-uniform; SPLIT: both waves of the block leave together
-    const int seg0 = SEG ? A.seg0 : part * (kWave * C);
-    const int segN = SEG ? A.segN : ((SPLIT > 1) ? min(A.N1 - seg0, kWave * C) : A.N1);
+    const long w = (long)xcd_remap(blockIdx.x, gridDim.x) * WPB + wib;
+    if (w >= (long)A.P * A.R) return; // wave-uniform
+    const int seg0 = SEG ? A.seg0 : 0;
+    const int segN = SEG ? A.segN : A.N1;
     const int lane = threadIdx.x & 63;
     const long pose = w / A.R;
     const int n0 = lane * C;
@@ -48,26 +43,11 @@ __global__ __launch_bounds__(kWave *WPB, (C <= 8 ? DIFFUS_FWD_MIN_WAVES : 1)) vo
     load_pose<PM>(ps, A.src, A.src_f64, A.dirs, A.dir_f64, pose, w);
 
     float zi[C], z[C], r[C], e[C], u0[C], u1[C], u2[C];
-#ifdef DIFFUS_ABLATE_GATHER
-#pragma unroll
-    for (int j = 0; j < C; ++j) zi[j] = ps.sf[0] + (float)(j * kWave + lane) * ps.df[1];
-#else
     gather_interleaved<C, SAMPLER, LAYOUT, false, PM>(A, seg0, segN, ps, lane, zi, u0, u1, u2);
-#endif
     STAMPW(1);
-#ifdef DIFFUS_ABLATE_TRANSPOSE
-#pragma unroll
-    for (int j = 0; j < C; ++j) z[j] = zi[j];
-#else
     to_chunked<C>(wb, lane, zi, z);
-#endif
     STAMPW(2);
     float zprev = lane_prev(z[C - 1], z[C - 1]); // last sample of the lane below (lane 0: unused unless a carry comes in)
-    if (SPLIT > 1) {
-        if (part == 0 && lane == kWave - 1) s_c[4] = z[C - 1];
-        __syncthreads();
-        if (part == 1 && lane == 0) zprev = s_c[4];
-    }
     Mat K = mat_identity(), Klast = mat_identity();
     if (cin) { // carry of the earlier segments: running product and the sample just before this segment
         K = Mat{cin[w * 5 + 0], cin[w * 5 + 1], cin[w * 5 + 2], cin[w * 5 + 3]};
@@ -76,32 +56,14 @@ __global__ __launch_bounds__(kWave *WPB, (C <= 8 ? DIFFUS_FWD_MIN_WAVES : 1)) vo
     float medv = (A.start > 0) ? A.med[pose] : 0.f;
     reflect_chunk<C>(A, seg0, segN, n0, z, zprev, medv, r);
     STAMPW(3);
-#ifdef DIFFUS_ABLATE_SCAN
-#pragma unroll
-    for (int j = 0; j < C; ++j) e[j] = r[j];
-#else
-    if (SPLIT > 1) {
-        auto exchange = [&](const Mat &Lincl, Mat &carry) -> bool {
-            if (part == 0 && lane == kWave - 1) {
-                s_c[0] = Lincl.a; s_c[1] = Lincl.b; s_c[2] = Lincl.c; s_c[3] = Lincl.d;
-            }
-            __syncthreads();
-            if (part == 0) return false;
-            carry = Mat{s_c[0], s_c[1], s_c[2], s_c[3]};
-            return true;
-        };
-        echo_chunk<C, true>(r, lane, e, nullptr, -1, nullptr, exchange);
-    } else {
-        echo_chunk<C, true>(r, lane, e, cin ? &K : nullptr, segN - 1, cout ? &Klast : nullptr);
-        // an ill-conditioned ray (wave-uniform, rare): the same scan in float64 (diffus_device.hpp).  A ray of one launch: in place; a
-        // ray of several (SEG) is flagged and walked again from its first sample by render_fwd_long_repair_kernel, its running
-        // product carried in float64 (a float32 carry would bring its own rounding times the ray's condition number along)
-        if (__builtin_expect(echo_needs_f64<C>(e), 0)) {
-            if (!SEG) echo_f64_rare<C, SAMPLER, LAYOUT, PM>(A, ps, seg0, segN, n0, medv, e);
-            else if (A.rflag && lane == 0) A.rflag[w * 2] = 1; // a ray of several launches: render_fwd_long_repair_kernel walks it again
-        }
+    echo_chunk<C, true>(r, lane, e, cin ? &K : nullptr, segN - 1, cout ? &Klast : nullptr);
+    // an ill-conditioned ray (wave-uniform, rare): the same scan in float64 (diffus_device.hpp).  A ray of one launch: in place; a
+    // ray of several (SEG) is flagged and walked again from its first sample by render_fwd_long_repair_kernel, its running
+    // product carried in float64 (a float32 carry would bring its own rounding times the ray's condition number along)
+    if (__builtin_expect(echo_needs_f64<C>(e), 0)) {
+        if (!SEG) echo_f64_rare<C, SAMPLER, LAYOUT, PM>(A, ps, seg0, segN, n0, medv, e);
+        else if (A.rflag && lane == 0) A.rflag[w * 2] = 1; // a ray of several launches: render_fwd_long_repair_kernel walks it again
     }
-#endif
     if (cout) { // hand the running product and the last impedance sample to the next segment
         const int last = segN - 1;
         if (lane == last / C) {
@@ -124,14 +86,7 @@ __global__ __launch_bounds__(kWave *WPB, (C <= 8 ? DIFFUS_FWD_MIN_WAVES : 1)) vo
     // the frame row leaves from the CHUNKED mapping: two 16-byte stores per lane (a wave's 2 KiB contiguous) instead of
     // an LDS transpose and eight dword stores
     float *out = A.frame + w * A.N1 + seg0;
-#ifdef DIFFUS_ABLATE_STORE
-    float acc = 0.f;
-#pragma unroll
-    for (int j = 0; j < C; ++j) acc += e[j];
-    if (acc == 123.456f) out[lane] = acc;
-#else
     store_chunk<C, true>(out, n0, segN, e);
-#endif
 
     STAMPW(6);
     if (A.idx) {
@@ -443,6 +398,93 @@ __global__ __launch_bounds__(kBlock) void render_fwd_long_repair_kernel(Args A)
     }
 }
 
+// ----------------------------------------------------------------------------
+// start > 0: median over rays of r[:, start] (reference :243), one block per pose.
+// Lower median like torch.median; NaN if any NaN.  Leaves the median ray's samples in medinfo for the backward.
+template <int SAMPLER, int LAYOUT>
+__global__ __launch_bounds__(kBlock) void median_kernel(Args A)
+{
+    extern __shared__ __attribute__((aligned(16))) float vals[];
+    __shared__ int s_nan;
+    const int pose = blockIdx.x;
+    if (threadIdx.x == 0) s_nan = 0;
+    __syncthreads();
+    // the two samples (steps start, start + 1) of a ray and, trilinear, their spatial gradients: mi[8] as in medinfo
+    auto sample_ray = [&](int i, float (&mi)[8]) {
+        Pose ps;
+        load_pose(ps, A.src, A.src_f64, A.dirs, A.dir_f64, pose, (long)pose * A.R + i);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int k = A.start + q;
+            const float p0 = ray_point(ps, 0, k), p1 = ray_point(ps, 1, k), p2 = ray_point(ps, 2, k);
+            if (SAMPLER == DIFFUS_NEAREST) {
+                const int i0 = nearest_index(p0, A.G.d0), i1 = nearest_index(p1, A.G.d1), i2 = nearest_index(p2, A.G.d2);
+                mi[q] = A.vol[vox_off<LAYOUT>(A.G, i0, i1, i2)];
+                mi[2 + 3 * q] = mi[3 + 3 * q] = mi[4 + 3 * q] = 0.f;
+            } else {
+                const TriSample sm = tri_sample<LAYOUT, true>(A.vol, A.G, p0, p1, p2);
+                mi[q] = sm.v;
+                mi[2 + 3 * q] = sm.g0; mi[3 + 3 * q] = sm.g1; mi[4 + 3 * q] = sm.g2;
+            }
+        }
+    };
+    // The first ray of a thread (every ray when R <= 256) keeps its samples in registers: the thread that turns out to
+    // hold the median writes them out without a second round trip to memory.
+    float mine[8];
+    for (int i = threadIdx.x; i < A.R; i += blockDim.x) {
+        float mi[8];
+        sample_ray(i, mi);
+        if (i == (int)threadIdx.x) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) mine[q] = mi[q];
+        }
+        const float v = reflect(mi[0], mi[1]);
+        vals[i] = v;
+        if (v != v) atomicOr(&s_nan, 1);
+    }
+    __syncthreads();
+    if (s_nan) {
+        if (threadIdx.x == 0) {
+            A.med[pose] = __builtin_nanf("");
+            A.who[pose] = -1;
+        }
+        return;
+    }
+    const int target = (A.R - 1) / 2;
+    for (int i = threadIdx.x; i < A.R; i += blockDim.x) {
+        const float v = vals[i];
+        int rank = 0;
+        int j = 0;
+#pragma unroll 4
+        for (; j + 4 <= A.R; j += 4) { // vals is 16-byte aligned dynamic LDS: one ds_read_b128 (a broadcast) per 4 values
+            const float4 u = *reinterpret_cast<const float4 *>(vals + j);
+            rank += (u.x < v) || (u.x == v && j < i);
+            rank += (u.y < v) || (u.y == v && j + 1 < i);
+            rank += (u.z < v) || (u.z == v && j + 2 < i);
+            rank += (u.w < v) || (u.w == v && j + 3 < i);
+        }
+        for (; j < A.R; ++j) {
+            const float u = vals[j];
+            rank += (u < v) || (u == v && j < i);
+        }
+        if (rank == target) { // exactly one i satisfies this
+            A.med[pose] = v;
+            A.who[pose] = i;
+            // what the backward needs to route d/d median to this ray (pose_finish_block)
+            float mi[8];
+            if (i == (int)threadIdx.x) {
+#pragma unroll
+                for (int q = 0; q < 8; ++q) mi[q] = mine[q];
+            } else {
+                sample_ray(i, mi);
+            }
+            float *out = A.medinfo + (long)pose * 8;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) out[q] = mi[q];
+        }
+    }
+}
+
 template <int SM, int LY, int PM>
 int launch_fwd_long_repair_t(const Args &A, hipStream_t st)
 {
@@ -460,13 +502,9 @@ int launch_fwd_t(const Args &A, hipStream_t st)
     case 2: hipLaunchKernelGGL((render_fwd_kernel<2, SM, LY, kWavesPerBlock, PM>), dim3(nblk), dim3(kBlock), 0, st, A); break;
     case 4: hipLaunchKernelGGL((render_fwd_kernel<4, SM, LY, kWavesPerBlock, PM>), dim3(nblk), dim3(kBlock), 0, st, A); break;
     case 8: hipLaunchKernelGGL((render_fwd_kernel<8, SM, LY, kWavesPerBlock, PM>), dim3(nblk), dim3(kBlock), 0, st, A); break;
-    default: // 512 < N1 <= 1024: one wave with 16 samples per lane (100 VGPRs).  The two-wave SPLIT form that pays for
-             // the backward (render_bwd.hip) does not here: 31.4 against 21.9 us at 8 poses x 512 rays x 1024 steps
-#ifdef DIFFUS_FWD_SPLIT
-        hipLaunchKernelGGL((render_fwd_kernel<8, SM, LY, 2, PM, false, 2>), dim3((unsigned)waves), dim3(2 * kWave), 0, st, A);
-#else
+    default: // 512 < N1 <= 1024: one wave with 16 samples per lane (100 VGPRs).  (Tried: the backward's two-wave SPLIT form,
+             // 31.4 against 21.9 us at 8 poses x 512 rays x 1024 steps.)
         hipLaunchKernelGGL((render_fwd_kernel<16, SM, LY, kWavesPerBlock, PM>), dim3(nblk), dim3(kBlock), 0, st, A);
-#endif
         break;
     }
     return last_launch();
@@ -492,6 +530,16 @@ int diffus::launch_fwd(const Args &A, int sampler, int layout, hipStream_t st)
         constexpr int SM = decltype(S_)::value, LY = decltype(L_)::value;
         if (A.N1 > DIFFUS_MAX_SAMPLES) return f32 ? launch_fwd_seg<SM, LY, 0>(A, st) : launch_fwd_seg<SM, LY, 1>(A, st);
         return f32 ? launch_fwd_t<SM, LY, 0>(A, st) : launch_fwd_t<SM, LY, 1>(A, st);
+    });
+}
+
+// median_kernel's launch, for the forward and the backward (render_bwd.hip)
+int diffus::launch_median(const Args &A, int sampler, int layout, hipStream_t st)
+{
+    return dispatch_sl(sampler, layout, [&](auto S_, auto L_) {
+        hipLaunchKernelGGL((median_kernel<decltype(S_)::value, decltype(L_)::value>), dim3(A.P), dim3(kBlock),
+                           sizeof(float) * (size_t)A.R, st, A);
+        return last_launch();
     });
 }
 
@@ -549,7 +597,7 @@ int diffus_render_fwd(const float *vol, int d0, int d1, int d2, int layout, cons
     A.frame = frame;
     A.idx = (long long *)idx;
     if (start > 0) {
-        rc = launch_median(A, sampler, layout, st);
+        rc = diffus::launch_median(A, sampler, layout, st);
         if (rc) return rc;
     }
     // rays longer than one launch covers: segments of DIFFUS_MAX_SAMPLES chained through the running product

@@ -1,4 +1,5 @@
-// scatter.hip -- volume-gradient scatter (LDS-privatised patches), sparse gradient flush, layout conversions
+// scatter.hip -- volume-gradient scatter of the backward (LDS-privatised patches), launch_scatter.  The sparse gradient
+// flush and the layout conversions are in layout.hip.
 #include "diffus_host.hpp"
 
 namespace {
@@ -61,17 +62,6 @@ __device__ __forceinline__ int tile_unit(int v, int axis)
 #ifndef DIFFUS_SC_MIN_BLOCKS
 #define DIFFUS_SC_MIN_BLOCKS 6
 #endif
-// stage probe (tools/): -DDIFFUS_SC_EXIT=n makes the planar path return after stage n with its values forced live
-#ifdef DIFFUS_SC_EXIT
-#define SC_EXIT(n)                                                                                                      \
-    if (DIFFUS_SC_EXIT == (n)) {                                                                                        \
-        _Pragma("unroll") for (int q_ = 0; q_ < kSPT; ++q_)                                                             \
-            asm volatile("" ::"v"(zb[q_]), "v"(tx[q_]), "v"(ty[q_]), "v"(x0[q_]), "v"(y0[q_]), "v"(x1[q_]), "v"(y1[q_])); \
-        return true;                                                                                                    \
-    }
-#else
-#define SC_EXIT(n) ((void)0)
-#endif
 constexpr int kScRays = DIFFUS_SC_PATCH_RAYS, kScSteps = DIFFUS_SC_PATCH_STEPS;
 constexpr int kSB = DIFFUS_SCATTER_THREADS, kSW = kSB / kWave, kSPT = kScRays * kScSteps / kSB;
 // Tile capacities in 32-bit entries.  kTileCap (24 KiB, 6 blocks per CU): the launch for fans the caller KNOWS to be planar
@@ -118,12 +108,6 @@ __device__ __forceinline__ bool scatter_patch_planar(const Args &A, double *tile
     float zb[kSPT];
     {
         const char *rb = reinterpret_cast<const char *>(rows);
-#ifdef DIFFUS_ABLATE_SC_LOAD // timing probes (tools/): the zbar values are made up, nothing is loaded
-        if (true) {
-#pragma unroll
-            for (int q = 0; q < kSPT; ++q) zb[q] = (ray_ok && nbase + q < A.N1) ? 1e-3f * (float)((tid + q) & 15) : 0.f;
-        } else
-#endif
         if (ray_ok && nbase + kSPT <= A.N1) {
             if constexpr (kSPT == 4) {
                 const F4a4 t = *reinterpret_cast<const F4a4 *>(rb + (size_t)row_off);
@@ -177,7 +161,6 @@ __device__ __forceinline__ bool scatter_patch_planar(const Args &A, double *tile
     bx[3] = has ? max(y1[0], y1[kSPT - 1]) : -1;
     if (tid == 0) *s_live = 0;
     STAMP(1);
-    SC_EXIT(1);
     bx[0] = wave_reduce_minmax<true>(bx[0]);
     bx[1] = wave_reduce_minmax<false>(bx[1]);
     bx[2] = wave_reduce_minmax<true>(bx[2]);
@@ -189,7 +172,6 @@ __device__ __forceinline__ bool scatter_patch_planar(const Args &A, double *tile
     }
     __syncthreads(); // also: the tile is clear
     STAMP(2);
-    SC_EXIT(2);
     // ---- block-uniform bookkeeping, on the scalar unit (readfirstlane): the boxes in BRICK units
     int wb[kSW][4];
     int all_planar = 1;
@@ -279,7 +261,6 @@ __device__ __forceinline__ bool scatter_patch_planar(const Args &A, double *tile
             continue;
         }
         STAMP(3);
-    SC_EXIT(3);
         // tile entry of voxel (x, y) = (x - 4 l0) * BY + (y - 4 l1), BY = 4 b1 voxels per row + 1 of padding: an ODD
         // row stride.  A thread's neighbours in the wave sit 4 steps further along the ray; for a ray that runs along
         // dim 0 that is 4 rows, and 4 rows of 4 b1 doubles are a multiple of the 64 banks whenever b1 is even: the 8
@@ -311,10 +292,6 @@ __device__ __forceinline__ bool scatter_patch_planar(const Args &A, double *tile
                 const float s0 = zb[q] * wa0, s1 = zb[q] * wa1;
                 c00 = s0 * wb0; c01 = s0 * wb1; c10 = s1 * wb0; c11 = s1 * wb1;
             }
-#ifdef DIFFUS_ABLATE_SC_ADD
-            asm volatile("" :: "v"(c00), "v"(c01), "v"(c10), "v"(c11), "v"(e00), "v"(e11));
-            continue;
-#endif
             const unsigned long long act = __builtin_amdgcn_ballot_w64(on); // (HIP's __ballot goes through an int: 2 VALU more)
             if (act == 0ull) continue; // wave-uniform
             const int lead = __builtin_ctzll(act);
@@ -353,7 +330,6 @@ __device__ __forceinline__ bool scatter_patch_planar(const Args &A, double *tile
         }
         __syncthreads();
         STAMP(4);
-    SC_EXIT(4);
         if (__builtin_amdgcn_readfirstlane(*s_live) == 0) continue; // no wave had a nonzero zbar: the tile is still clear (block-uniform)
         // flush: a half-wave = one brick column = the 32 floats (x & 3, y & 3, z) of its brick(s); two lanes share a
         // tile entry and apply the two depth weights.  z0 even: one brick, a contiguous 128-B atomic run.
@@ -394,16 +370,12 @@ __device__ __forceinline__ bool scatter_patch_planar(const Args &A, double *tile
             auto emit_pair = [&](unsigned grow, int cp, double v, unsigned ta) {
                 if (nsub > 1 && v != 0.0 && !(o & 1)) *reinterpret_cast<double *>(const_cast<char *>(tile_b) + ta) = 0.0; // leave the tile clean for the next group
                 const bool nz = v != 0.0 && adds;
-#ifdef DIFFUS_ABLATE_SC_FLUSH
-                asm volatile("" :: "s"(grow), "v"((float)v * wz), "v"(nz));
-#else
                 if (nz) {
                     const unsigned gb = grow + 2u * (unsigned)cp * nb2u; // brick index of the pair's first column at depth brick 0
                     // every adding lane marks its brick (lanes of a brick store the same word: one write)
                     if (A.gtouched) *reinterpret_cast<int *>(gt_b + (size_t)gb * 4u + (size_t)lc_t) = 1;
                     atomicAdd(reinterpret_cast<float *>(gvol_b + (size_t)gb * (kBrickFloats * 4u) + (size_t)lc_g), (float)v * wz);
                 }
-#endif
             };
             const int npr = (b1 + 1) >> 1; // column pairs per brick row, in the box
             for (int ci = wv >> 1; ci < b0; ci += 2) {
@@ -430,233 +402,6 @@ __device__ __forceinline__ bool scatter_patch_planar(const Args &A, double *tile
         if (sp + 1 < nsub) __syncthreads();
     }
     return true;
-}
-
-
-// ---- MERGED planar patches: the part of a fan that has left the volume -------------------------------------------------
-// Rays that have left the volume are clamped onto its faces (grid_sample's border rule): a patch of them touches a line or a
-// corner of border voxels -- a few dozen tile entries -- and still pays the whole skeleton of a block (pose and zbar loads,
-// tile clear, boxes, two barriers, bookkeeping, flush walk): 16-18 k cycles whatever the tile holds, tools/scatter_stamps.py;
-// 39 % of the blocks of config 3 are of that kind.  A ray that is outside stays outside (the volume is convex), so once the two
-// EDGE rays of a ray group are outside at the first step of a step group, the kernel lets ONE block (the "leader") take that
-// step group and the following ones up to the next multiple of four, through ONE tile and ONE skeleton; the blocks of the
-// groups it covers ("followers") exit at once.  Leader and followers decide by the same rule from the same two rays, so every
-// sample is scattered exactly once whatever the rays in between do (if they are NOT all outside, the union box is merely
-// larger; if it does not fit the tile, or a ray turns out not to be planar, the leader adds its samples straight to memory --
-// correct, slow, and not seen in any fan of the reference).
-// rows / row_off / nbase: as in scatter_patch_planar, for the leader's own (first) step group; ng: step groups it takes.
-template <int SAMPLER, int PM, int CAP>
-__device__ __forceinline__ void scatter_patch_planar_merged(const Args &A, double *tile, int (*s_box)[4], int *s_planar, int *s_live, const Pose &ps,
-                                                            const float *rows, unsigned row_off, bool ray_ok, int nbase, int ng, int tid)
-{
-    constexpr int kCapD = CAP / 2, kMaxG = 4;
-    const int wib = tid >> 6;
-    // every group's zbar values first (ng x 16 bytes per thread in flight), the tile cleared under them
-    float zb[kMaxG][kSPT];
-    {
-        const char *rb = reinterpret_cast<const char *>(rows);
-#pragma unroll
-        for (int g = 0; g < kMaxG; ++g) {
-            const int n0 = nbase + g * kScSteps;
-            const unsigned off = row_off + (unsigned)(g * kScSteps) * 4u;
-            if (g < ng && ray_ok && n0 + kSPT <= A.N1) {
-                if constexpr (kSPT == 4) {
-                    const F4a4 t = *reinterpret_cast<const F4a4 *>(rb + (size_t)off);
-                    zb[g][0] = t.x; zb[g][1] = t.y; zb[g][2] = t.z; zb[g][3] = t.w;
-                } else {
-#pragma unroll
-                    for (int q = 0; q < kSPT; ++q) zb[g][q] = ldb_f32(rows, off + 4u * q);
-                }
-            } else {
-#pragma unroll
-                for (int q = 0; q < kSPT; ++q) zb[g][q] = (g < ng && ray_ok && n0 + q < A.N1) ? ldb_f32(rows, off + 4u * q) : 0.f;
-            }
-        }
-    }
-    {
-        int4 *t4 = reinterpret_cast<int4 *>(tile);
-#pragma unroll
-        for (int e = 0; e < CAP / 4 / kSB; ++e) t4[e * kSB + tid] = make_int4(0, 0, 0, 0);
-    }
-    const bool ray_planar = (PM == 0 || ps.pmode != 2) ? (ps.df[2] == 0.f) : (ps.dd[2] == 0.0);
-    const bool wave_planar = __ballot(ray_planar) == ~0ull;
-    auto cell_xy = [&](int n, int &x0, int &x1, int &y0, int &y1, float &tx, float &ty) {
-        const float kf = (float)(A.start + n);
-        const float p0 = ray_point_f<PM>(ps, 0, kf), p1 = ray_point_f<PM>(ps, 1, kf);
-        if (SAMPLER == DIFFUS_NEAREST) {
-            x0 = x1 = nearest_index(p0, A.G.d0); y0 = y1 = nearest_index(p1, A.G.d1);
-            tx = ty = 0.f;
-        } else {
-            const Axis a = tri_axis(p0, A.G.d0), b = tri_axis(p1, A.G.d1);
-            x0 = a.i0; x1 = a.i1; tx = a.t; y0 = b.i0; y1 = b.i1; ty = b.t;
-        }
-    };
-    // box: a ray is a straight line and clamp / floor are monotone, so the extremes of a thread's samples over the whole merged
-    // range sit at its first and its last one
-    int bx[4];
-    {
-        int ax0, ax1, ay0, ay1, bx0, bx1, by0, by1;
-        float t0, t1;
-        cell_xy(nbase, ax0, ax1, ay0, ay1, t0, t1);
-        cell_xy(nbase + (ng - 1) * kScSteps + kSPT - 1, bx0, bx1, by0, by1, t0, t1);
-        const bool has = ray_ok && nbase < A.N1;
-        bx[0] = has ? min(ax0, bx0) : 0x7fffffff; bx[1] = has ? max(ax1, bx1) : -1;
-        bx[2] = has ? min(ay0, by0) : 0x7fffffff; bx[3] = has ? max(ay1, by1) : -1;
-    }
-    if (tid == 0) *s_live = 0;
-    bx[0] = wave_reduce_minmax<true>(bx[0]);
-    bx[1] = wave_reduce_minmax<false>(bx[1]);
-    bx[2] = wave_reduce_minmax<true>(bx[2]);
-    bx[3] = wave_reduce_minmax<false>(bx[3]);
-    if ((tid & 63) == 63) {
-        s_planar[wib] = wave_planar;
-#pragma unroll
-        for (int a = 0; a < 4; ++a) s_box[wib][a] = bx[a];
-    }
-    __syncthreads(); // also: the tile is clear
-    int all_planar = 1, mn0 = 0x7fffffff, mx0 = -1, mn1 = 0x7fffffff, mx1 = -1;
-#pragma unroll
-    for (int wv = 0; wv < kSW; ++wv) {
-        all_planar &= s_planar[wv];
-        mn0 = min(mn0, __builtin_amdgcn_readfirstlane(s_box[wv][0]) >> 2); mx0 = max(mx0, __builtin_amdgcn_readfirstlane(s_box[wv][1]) >> 2);
-        mn1 = min(mn1, __builtin_amdgcn_readfirstlane(s_box[wv][2]) >> 2); mx1 = max(mx1, __builtin_amdgcn_readfirstlane(s_box[wv][3]) >> 2);
-    }
-    if (mx0 < 0 || mx1 < 0) return; // no sample at all (block-uniform)
-    const int l0 = mn0, l1 = mn1, b0 = mx0 - mn0 + 1, b1 = mx1 - mn1 + 1;
-    const unsigned need = min(4u * (unsigned)min(b0, 0x3fff) * (4u * (unsigned)min(b1, 0x3fff) + kRowPad), (unsigned)kCapD + 1u);
-    if (!__builtin_amdgcn_readfirstlane(all_planar) || need > (unsigned)kCapD) {
-        // not planar after all (a wrong DIFFUS_FANS_PLANAR promise), or the union box exceeds the tile: every sample straight to
-        // memory with its full 3-D cell
-#pragma unroll 1
-        for (int g = 0; g < ng; ++g)
-#pragma unroll 1
-            for (int q = 0; q < kSPT; ++q) {
-                float v = 0.f;
-#pragma unroll
-                for (int gg = 0; gg < kMaxG; ++gg)
-#pragma unroll
-                    for (int qq = 0; qq < kSPT; ++qq) v = (gg == g && qq == q) ? zb[gg][qq] : v;
-                if (!finitef(v) || v == 0.f) continue;
-                const Cell c = cell_of<SAMPLER, PM>(A, ps, A.start + nbase + g * kScSteps + q);
-                for_each_corner<SAMPLER>(c, v, [&](int i, int j, int k, float w) {
-                    if (w != 0.f) {
-                        const unsigned gi = vox_off<DIFFUS_BRICKED>(A.G, i, j, k);
-                        atomicAdd(A.gvol + gi, w);
-                        if (A.gtouched) A.gtouched[gi >> 5] = 1;
-                    }
-                });
-            }
-        return;
-    }
-    // the patch's dim-2 cell: the same for every sample of a planar fan
-    int iz0, iz1;
-    float tz;
-    {
-        const float p2 = ray_point_f<PM>(ps, 2, 0.f);
-        if (SAMPLER == DIFFUS_NEAREST) {
-            iz0 = iz1 = nearest_index(p2, A.G.d2);
-            tz = 0.f;
-        } else {
-            const Axis c = tri_axis(p2, A.G.d2);
-            iz0 = c.i0; iz1 = c.i1; tz = c.t;
-        }
-        iz0 = __builtin_amdgcn_readfirstlane(iz0); iz1 = __builtin_amdgcn_readfirstlane(iz1);
-        tz = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(tz)));
-    }
-    const int BY = 4 * b1 + kRowPad;
-    const int org = -(4 * l0) * BY - 4 * l1;
-    const int BY8 = BY * 8, org8 = org * 8;
-    char *tile_c = reinterpret_cast<char *>(tile);
-    auto add_at = [&](int byte_off, double v) { atomicAdd(reinterpret_cast<double *>(tile_c + byte_off), v); };
-    unsigned nz = 0;
-    // ---- accumulate, group after group (the code of scatter_patch_planar's accumulation; see there for the same-cell path)
-#pragma unroll
-    for (int g = 0; g < kMaxG; ++g) {
-        if (g >= ng) break; // block-uniform
-#pragma unroll
-        for (int q = 0; q < kSPT; ++q) {
-            float zq = zb[g][q];
-            if (!finitef(zq)) zq = 0.f;
-            nz |= __float_as_uint(zq) & 0x7fffffffu;
-            const unsigned long long act = __builtin_amdgcn_ballot_w64(zq != 0.f);
-            if (act == 0ull) continue; // wave-uniform
-            int x0, x1, y0, y1;
-            float tx, ty;
-            cell_xy(nbase + g * kScSteps + q, x0, x1, y0, y1, tx, ty);
-            const int r0 = __mul24(x0, BY8) + org8, r1 = __mul24(x1, BY8) + org8;
-            const int e00 = r0 + 8 * y0, e11 = r1 + 8 * y1;
-            float c00, c01 = 0.f, c10 = 0.f, c11 = 0.f;
-            if constexpr (SAMPLER == DIFFUS_NEAREST) {
-                c00 = zq;
-            } else {
-                const float wa1 = tx, wa0 = 1.f - wa1, wb1 = ty, wb0 = 1.f - wb1;
-                const float s0 = zq * wa0, s1 = zq * wa1;
-                c00 = s0 * wb0; c01 = s0 * wb1; c10 = s1 * wb0; c11 = s1 * wb1;
-            }
-            const int lead = __builtin_ctzll(act);
-            const int f00 = __builtin_amdgcn_readlane(e00, lead), f11 = __builtin_amdgcn_readlane(e11, lead);
-            const unsigned long long eq = __builtin_amdgcn_ballot_w64(e00 == f00) & __builtin_amdgcn_ballot_w64(e11 == f11);
-            if ((eq & act) == act && __builtin_popcountll(act) > 4) { // wave-uniform: one cell for every live lane
-                const int f01 = __builtin_amdgcn_readlane(r0 + 8 * y1, lead), f10 = __builtin_amdgcn_readlane(r1 + 8 * y0, lead);
-                const double t00 = wave_sum_to_lane63((double)c00);
-                double t01 = 0.0, t10 = 0.0, t11 = 0.0;
-                if constexpr (SAMPLER != DIFFUS_NEAREST) {
-                    t01 = wave_sum_to_lane63((double)c01);
-                    t10 = wave_sum_to_lane63((double)c10);
-                    t11 = wave_sum_to_lane63((double)c11);
-                }
-                if ((tid & 63) == 63) {
-                    if (t00 != 0.0) add_at(f00, t00);
-                    if (t01 != 0.0) add_at(f01, t01);
-                    if (t10 != 0.0) add_at(f10, t10);
-                    if (t11 != 0.0) add_at(f11, t11);
-                }
-            } else {
-                if (c00 != 0.f) add_at(e00, (double)c00);
-                if constexpr (SAMPLER != DIFFUS_NEAREST) {
-                    if (c01 != 0.f) add_at(r0 + 8 * y1, (double)c01);
-                    if (c10 != 0.f) add_at(r1 + 8 * y0, (double)c10);
-                    if (c11 != 0.f) add_at(e11, (double)c11);
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    if (__builtin_amdgcn_ballot_w64(nz != 0u) != 0ull && (tid & 63) == 63) *s_live = 1;
-    __syncthreads();
-    if (__builtin_amdgcn_readfirstlane(*s_live) == 0) return; // nothing added: the tile is still clear (block-uniform)
-    // ---- flush (scatter_patch_planar's, for one group of waves): a wave takes two adjacent brick columns of one brick row
-    {
-        const int lane = tid & 63, o = lane & 31, h = lane >> 5;
-        const int zz = (o & 1) ? iz1 : iz0;
-        const float wz = (iz1 == iz0) ? ((o & 1) ? 0.f : 1.f) : ((o & 1) ? tz : 1.f - tz);
-        const bool adds = wz != 0.f, h0 = h == 0;
-        const unsigned lc_tile = (unsigned)((__mul24(o >> 3, BY) + 4 * h + ((o >> 1) & 3)) * 8);
-        const unsigned lc_g = (__umul24((unsigned)h, (unsigned)A.G.nb2) + (unsigned)(zz >> 1)) * kBrickFloats * 4u
-                              + (unsigned)(((o >> 1) << 1) + (zz & 1)) * 4u;
-        const unsigned lc_t = (__umul24((unsigned)h, (unsigned)A.G.nb2) + (unsigned)(zz >> 1)) * 4u;
-        unsigned lc_tile_o = lc_tile;
-        asm volatile("" : "+v"(lc_tile_o));
-        const char *tile_b = reinterpret_cast<const char *>(tile);
-        const int wv = __builtin_amdgcn_readfirstlane(wib);
-        const unsigned nb2u = (unsigned)A.G.nb2;
-        char *const gvol_b = reinterpret_cast<char *>(A.gvol);
-        char *const gt_b = reinterpret_cast<char *>(A.gtouched);
-        const int npr = (b1 + 1) >> 1;
-        for (int ci = wv >> 1; ci < b0; ci += 2) {
-            const unsigned trow = (unsigned)(4 * ci * BY) * 8u;
-            const unsigned grow = ((unsigned)(l0 + ci) * (unsigned)A.G.nb1 + (unsigned)l1) * nb2u;
-            for (int cp = wv & 1; cp < npr; cp += 2) {
-                const bool second = 2 * cp + 1 < b1; // wave-uniform
-                const double v = (h0 || second) ? *reinterpret_cast<const double *>(tile_b + trow + 64u * (unsigned)cp + lc_tile_o) : 0.0;
-                if (v != 0.0 && adds) {
-                    const unsigned gb = grow + 2u * (unsigned)cp * nb2u;
-                    if (A.gtouched) *reinterpret_cast<int *>(gt_b + (size_t)gb * 4u + (size_t)lc_t) = 1;
-                    atomicAdd(reinterpret_cast<float *>(gvol_b + (size_t)gb * (kBrickFloats * 4u) + (size_t)lc_g), (float)v * wz);
-                }
-            }
-        }
-    }
 }
 
 // ---- SLAB patches (bricked gradient): fans that are NOT planar in dim 2 --------------------------------------------
@@ -1202,7 +947,7 @@ __global__ __launch_bounds__(kSB, SLAB ? DIFFUS_SLAB_MIN_BLOCKS : DIFFUS_SC_MIN_
     // in flight at any time are then spread over all poses and ray groups (round 1: all depths of a few neighbouring fans
     // at a time was 58 against 52 us) AND over all depths (round 4).  Within a row the XCD remap keeps a pose on one XCD.
     const int tid = threadIdx.x;
-    int pose, nbase, sg_blk = 0; // (sg_blk: the block's step group)
+    int pose, nbase;
     bool ray_ok;
     long w, w0;        // this thread's ray, the block's first ray (block-uniform)
     unsigned row_off;  // bytes from zbar[w0][0] to the thread's first sample
@@ -1220,7 +965,6 @@ __global__ __launch_bounds__(kSB, SLAB ? DIFFUS_SLAB_MIN_BLOCKS : DIFFUS_SC_MIN_
         // window of rows AND every row a mix of depths: 28.4 -> 25.5 us at 32 poses, 178.6 -> 145.2 us at 256 (round 4).
         const int row = (int)by - has_finish;
         const int sg = (int)(((unsigned)row * (unsigned)sg_mul + 3u * (unsigned)pose) % (unsigned)step_groups);
-        sg_blk = sg;
         // thread -> ray (tid / 8) and 4 consecutive steps ((tid % 8) * 4 ..).  (Tried: a wave taking every 4th ray of the
         // patch instead of 8 adjacent ones, so that near the apex -- adjacent rays less than a voxel apart -- fewer lanes of
         // one LDS atomic share an address: 29.9 -> 30.5 us.)
@@ -1232,27 +976,10 @@ __global__ __launch_bounds__(kSB, SLAB ? DIFFUS_SLAB_MIN_BLOCKS : DIFFUS_SC_MIN_
         row_off = (__umul24((unsigned)(ray_ok ? rl : 0), (unsigned)A.N1) + (unsigned)nbase) * 4u; // N1 < 2^24, rl < 2^6
     };
     unsigned bx = blockIdx.x, by = blockIdx.y;
-#ifdef DIFFUS_SC_EXIT
-    if (DIFFUS_SC_EXIT == 0) return; // launch + dispatch floor
-#endif
     if (xcd_remap(bx, gridDim.x) >= (unsigned)A.P * (unsigned)ray_groups) return; // padding block (block-uniform, before any barrier)
     decode(bx, by);
 
     STAMP(0);
-#ifdef DIFFUS_SC_SALU_PAD // issue-rate probe (tools/): N extra scalar instructions per wave
-    {
-        int pad = 0;
-        asm volatile(".rept %1\n s_add_u32 %0, %0, 1\n .endr" : "+s"(pad) : "n"(DIFFUS_SC_SALU_PAD));
-        asm volatile("" :: "s"(pad));
-    }
-#endif
-#ifdef DIFFUS_SC_VALU_PAD // issue-rate probe (tools/): N extra vector instructions per wave
-    {
-        int pad = tid;
-        asm volatile(".rept %1\n v_add_u32 %0, %0, 1\n .endr" : "+v"(pad) : "n"(DIFFUS_SC_VALU_PAD));
-        asm volatile("" :: "v"(pad));
-    }
-#endif
     Pose ps;
     if constexpr (PM == 0) { // float32 pose: the source from the scalar unit, the direction at a 32-bit offset from a scalar base
         const float *sp = (const float *)A.src + (long)pose * 3, *dp = (const float *)A.dirs + w0 * 3;
@@ -1265,43 +992,6 @@ __global__ __launch_bounds__(kSB, SLAB ? DIFFUS_SLAB_MIN_BLOCKS : DIFFUS_SC_MIN_
         ps.pmode = 0;
     } else {
         load_pose<PM>(ps, A.src, A.src_f64, A.dirs, A.dir_f64, pose, w);
-    }
-#ifndef DIFFUS_SC_MERGE
-#define DIFFUS_SC_MERGE 1 // step groups a leader takes at most (1, 2 or 4).  OFF: measured slower at 32 and 64 poses, DESIGN fact 42
-#endif
-    if constexpr (kCanPlanar && !SLAB && PM == 0 && DIFFUS_SC_MERGE > 1) {
-        // The part of the fan that has left the volume: one block per up to four step groups (scatter_patch_planar_merged).
-        // The rule, evaluated identically by the leader and by the blocks it relieves: a step group is "outside" when the ray
-        // group's two edge rays are outside the slice at its first step; outside groups are taken in runs that end at multiples of
-        // four -- the leader of a run is its first group (a multiple of four, or an outside group whose predecessor is not).
-        if (A.fans_planar) {
-            const float *sp = (const float *)A.src + (long)pose * 3;
-            const int nr = min(kScRays, A.R - (int)(w0 - (long)pose * A.R));
-            const float *da = (const float *)A.dirs + w0 * 3, *db = (const float *)A.dirs + (w0 + nr - 1) * 3; // block-uniform: scalar loads
-            const float hx = (float)(A.G.d0 - 1), hy = (float)(A.G.d1 - 1);
-            auto outside = [&](int sgq) -> bool {
-                const float kf = (float)(A.start + sgq * kScSteps);
-                const float ax = __fadd_rn(sp[0], __fmul_rn(kf, da[0])), ay = __fadd_rn(sp[1], __fmul_rn(kf, da[1]));
-                const float bxp = __fadd_rn(sp[0], __fmul_rn(kf, db[0])), byp = __fadd_rn(sp[1], __fmul_rn(kf, db[1]));
-                const bool oa = !(ax > 0.f && ax < hx && ay > 0.f && ay < hy), ob = !(bxp > 0.f && bxp < hx && byp > 0.f && byp < hy);
-                return oa && ob;
-            };
-            if (__builtin_amdgcn_readfirstlane((int)outside(sg_blk))) {
-                constexpr int kMg = DIFFUS_SC_MERGE;
-                const bool leader = (sg_blk & (kMg - 1)) == 0 || !__builtin_amdgcn_readfirstlane((int)outside(sg_blk - 1));
-                if (!leader) return; // covered by the leader of its run (block-uniform, before any barrier)
-                // its run: the consecutive outside groups from here to the next multiple of four (a source outside the volume makes
-                // "outside" true BEFORE the rays enter as well: a run must end where the rule stops relieving blocks)
-                const int lim = min(kMg - (sg_blk & (kMg - 1)), step_groups - sg_blk);
-                int ng = 1;
-                while (ng < lim && __builtin_amdgcn_readfirstlane((int)outside(sg_blk + ng))) ++ng;
-                if (ng > 1) {
-                    scatter_patch_planar_merged<SAMPLER, PM, CAP>(A, reinterpret_cast<double *>(tile), s_box, s_planar, &s_live, ps, A.zbar + w0 * A.N1,
-                                                                  row_off, ray_ok, nbase, ng, tid);
-                    return;
-                }
-            }
-        }
     }
     if constexpr (kCanPlanar) {
         // The launch that carries the slab path asks the block's FIRST ray before it tries the planar path (a scalar load, no
@@ -1612,340 +1302,9 @@ int launch_scatter(const Args &A, int sampler, int layout, hipStream_t st)
 }
 } // namespace diffus
 
-namespace {
-
-// ----------------------------------------------------------------------------
-// canonical <-> bricked conversion.  A block moves 4 x 4 x 64 voxels (32 bricks,
-// 4 KiB): 16 canonical rows of 256 B on one side, 4 KiB contiguous on the other,
-// through an LDS transpose so that both sides are coalesced.
-constexpr int kConvZ = 64, kConvZThin = 8; // depths per block: whole volumes / thin sub-boxes (diffus_convert_volume_box)
-template <bool TO_BRICKED, bool ACCUMULATE, int CZ = kConvZ>
-__global__ __launch_bounds__(kBlock) void brick_convert_kernel(const float *__restrict__ in, float *__restrict__ out,
-                                                               Geom G, int zblk0 = 0, int by_0 = 0, int bx_0 = 0)
-{
-    __shared__ float t[16][CZ + 1];
-    // (zblk0, by_0, bx_0): the first block of a sub-box conversion (diffus_convert_volume_box); 0 for a whole volume
-    const int bz0 = ((int)blockIdx.x + zblk0) * (CZ / 2); // first brick along dim 2
-    const int by = blockIdx.y + by_0, bx = blockIdx.z + bx_0;
-    const int tid = threadIdx.x;
-    const long brick0 = ((long)bx * G.nb1 + by) * G.nb2 + bz0;
-    if (TO_BRICKED) {
-        for (int e = tid; e < 16 * CZ; e += kBlock) {
-            int row = e / CZ, zz = e - row * CZ;
-            int x = bx * 4 + (row >> 2), y = by * 4 + (row & 3), z = bz0 * 2 + zz;
-            t[row][zz] = (x < G.d0 && y < G.d1 && z < G.d2) ? in[((long)x * G.d1 + y) * G.d2 + z] : 0.f;
-        }
-        __syncthreads();
-        for (int e = tid; e < 16 * CZ; e += kBlock) {
-            int brick = e >> 5, off = e & 31;
-            if (bz0 + brick < G.nb2) out[(brick0 + brick) * kBrickFloats + off] = t[off >> 1][brick * 2 + (off & 1)];
-        }
-    } else {
-        for (int e = tid; e < 16 * CZ; e += kBlock) {
-            int brick = e >> 5, off = e & 31;
-            if (bz0 + brick < G.nb2) t[off >> 1][brick * 2 + (off & 1)] = in[(brick0 + brick) * kBrickFloats + off];
-        }
-        __syncthreads();
-        for (int e = tid; e < 16 * CZ; e += kBlock) {
-            int row = e / CZ, zz = e - row * CZ;
-            int x = bx * 4 + (row >> 2), y = by * 4 + (row & 3), z = bz0 * 2 + zz;
-            if (x < G.d0 && y < G.d1 && z < G.d2) {
-                long o = ((long)x * G.d1 + y) * G.d2 + z;
-                if (ACCUMULATE)
-                    out[o] += t[row][zz];
-                else
-                    out[o] = t[row][zz];
-            }
-        }
-    }
-}
-
-// Bricked gradient scratch -> canonical tensor.  Every touched brick (flag != 0) is added into (or stored to) the
-// canonical tensor, ZEROED in the bricked buffer and its flag cleared, so the bricked buffer and the flags are all-zero
-// again afterwards.  A fan touches a few thousand of the 524 288 bricks of a 256^3 volume: this replaces a 64 MiB memset
-// plus a 128 MiB dense conversion per step.
-// mode DIFFUS_FLUSH_PERSISTENT: `out` is a gradient tensor the caller keeps across steps and only this call writes.
-// A brick stored this step gets flag 2 ("out holds last step's values, scratch is zero"); if the next step does not
-// touch it again (the scatter overwrites the flag with 1) its voxels are zeroed in `out` and the flag cleared.  `out`
-// therefore always equals the dense gradient of the latest step without ever being memset.
-// mode DIFFUS_FLUSH_DENSE (this kernel): every voxel of `out` is written, one lane per brick.
-__global__ __launch_bounds__(kBlock) void gradbuf_flush_dense_kernel(float *__restrict__ bricked, int *__restrict__ touched,
-                                                                     float *__restrict__ out, Geom G, long nbricks)
-{
-    const int wib = threadIdx.x >> 6;
-    const long w = (long)blockIdx.x * kWavesPerBlock + wib;
-    const int lane = threadIdx.x & 63;
-    const long b0 = w * kWave;
-    if (b0 >= nbricks) return;
-    const long mine = b0 + lane;
-    int f = (mine < nbricks) ? touched[mine] : 0;
-    {
-        // EVERY voxel of `out` is written: a lane takes one brick, the wave 64 consecutive ones -- consecutive along dim 2,
-        // so that each of a brick's 16 (x, y) rows is a 512-byte run of the canonical tensor across the wave.
-        if (mine >= nbricks) return;
-        if (f) touched[mine] = 0;
-        const bool live = f == 1; // 2 = left by a PERSISTENT flush: the scratch is already zero there
-        const unsigned um = (unsigned)mine, t = um / (unsigned)G.nb2, bz = um - t * (unsigned)G.nb2;
-        const unsigned bx = t / (unsigned)G.nb1, by = t - bx * (unsigned)G.nb1;
-        float *bsrc = bricked + mine * kBrickFloats;
-        const int z = (int)bz * 2;
-#pragma unroll 4
-        for (int row = 0; row < 16; ++row) {
-            const int x = (int)bx * 4 + (row >> 2), y = (int)by * 4 + (row & 3);
-            float2 v = make_float2(0.f, 0.f);
-            if (live) {
-                v = *reinterpret_cast<const float2 *>(bsrc + row * 2);
-                *reinterpret_cast<float2 *>(bsrc + row * 2) = make_float2(0.f, 0.f);
-            }
-            if (x < G.d0 && y < G.d1) {
-                float *o = out + ((long)x * G.d1 + y) * G.d2 + z;
-                if (z + 1 < G.d2 && !(G.d2 & 1)) {
-                    *reinterpret_cast<float2 *>(o) = v;
-                } else {
-                    o[0] = v.x;
-                    if (z + 1 < G.d2) o[1] = v.y;
-                }
-            }
-        }
-        return;
-    }
-}
-
-// The sparse modes.  A wave reads the flags of 256 consecutive bricks (four coalesced loads), compacts the ids of the
-// touched ones into LDS and walks them EIGHT per trip: 8 lanes per brick, a lane moving four floats = the z pairs of two
-// neighbouring (x, y) rows.  (Rounds 2-3: 64 bricks per wave, two per trip -- 2048 blocks whose launch and flag reads were
-// most of the kernel at 32 poses; 256 bricks per wave at two per trip was slower there, the serial walk four times longer.)
-constexpr int kFlushBricks = 256;
-template <bool VEC2> // VEC2: d2 even and `out` 8-byte aligned -- a z pair is one aligned 8-byte word of the canonical tensor
-__global__ __launch_bounds__(kBlock) void gradbuf_flush_kernel(float *__restrict__ bricked, int *__restrict__ touched,
-                                                               float *__restrict__ out, Geom G, long nbricks, int mode)
-{
-    __shared__ short s_list[kWavesPerBlock][kFlushBricks];
-    const int wib = threadIdx.x >> 6;
-    const long w = (long)blockIdx.x * kWavesPerBlock + wib;
-    const int lane = threadIdx.x & 63;
-    const long b0 = w * kFlushBricks;
-    if (b0 >= nbricks) return;
-    int f[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const long mine = b0 + c * kWave + lane;
-        f[c] = (mine < nbricks) ? touched[mine] : 0;
-    }
-    if (__ballot((f[0] | f[1] | f[2] | f[3]) != 0) == 0ull) return; // wave-uniform: nothing touched in these 256 bricks
-    int cnt = 0;
-    const unsigned long long below = (1ull << lane) - 1;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const unsigned long long m = __ballot(f[c] != 0);
-        if (f[c]) {
-            touched[b0 + c * kWave + lane] = (mode == DIFFUS_FLUSH_PERSISTENT && f[c] == 1) ? 2 : 0;
-            // bit 8 marks a stale brick (nothing new this step: clear what the last step left in `out`)
-            s_list[wib][cnt + __builtin_popcountll(m & below)] = (short)((c * kWave + lane) | (f[c] == 2 ? 256 : 0));
-        }
-        cnt += __builtin_popcountll(m);
-    }
-    wave_lds_sync();
-    const int sub = lane & 7, grp = lane >> 3;
-    // the lane's two rows inside a brick: x = sub / 2, y = 2 (sub % 2) and the next one; floats 4 sub .. 4 sub + 3
-    const int xl = sub >> 1, yl = (sub & 1) * 2;
-#pragma unroll 2
-    for (int i = grp; i < cnt; i += 8) { // trips are independent: their loads overlap
-        const int e = s_list[wib][i];
-        const long brick = b0 + (e & 255);
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (!(e & 256)) { // uniform over the brick's 8 lanes
-            float4 *src = reinterpret_cast<float4 *>(bricked + brick * kBrickFloats + sub * 4);
-            v = *src;
-            *src = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        // 32-bit index arithmetic (a volume has fewer than 2^25 bricks)
-        const unsigned ub = (unsigned)brick, t = ub / (unsigned)G.nb2, bz = ub - t * (unsigned)G.nb2;
-        const unsigned bx = t / (unsigned)G.nb1, by = t - bx * (unsigned)G.nb1;
-        const int x = (int)bx * 4 + xl, y = (int)by * 4 + yl, z = (int)bz * 2;
-        if (x >= G.d0) continue;
-        float *o = out + ((long)x * G.d1 + y) * G.d2 + z;
-#pragma unroll
-        for (int r = 0; r < 2; ++r, o += G.d2) {
-            if (y + r >= G.d1) break;
-            const float v0 = r ? v.z : v.x, v1 = r ? v.w : v.y;
-            if (VEC2) { // z + 1 < d2 always: d2 is even
-                float2 *o2 = reinterpret_cast<float2 *>(o);
-                if (mode == DIFFUS_FLUSH_ACCUMULATE) {
-                    const float2 q = *o2;
-                    *o2 = make_float2(q.x + v0, q.y + v1);
-                } else {
-                    *o2 = make_float2(v0, v1);
-                }
-            } else {
-                o[0] = (mode == DIFFUS_FLUSH_ACCUMULATE) ? o[0] + v0 : v0;
-                if (z + 1 < G.d2) o[1] = (mode == DIFFUS_FLUSH_ACCUMULATE) ? o[1] + v1 : v1;
-            }
-        }
-    }
-}
-
-// canonical -> PAIRED: a block writes the records of TWO neighbouring 4 x 4 column blocks for 128 depths (two runs of
-// 128 x 160 B) from 4 x 9 canonical rows of 129 floats (the ninth column and the 129th depth are the neighbours the
-// records repeat, clamped at the volume's edge), through LDS so that both sides are coalesced: 512-byte row reads,
-// 16-byte stores.  256^3: 42 us = 5.5 TB/s of (volume read + records written).  (First version: one column block x 32
-// depths per block, 132-byte row reads, a quarter of them the halo column: the L2-side fetch was 1.9x the volume and
-// the kernel took 80 us; 64 depths per block: 46 us.)
-#ifndef DIFFUS_PC_Z
-#define DIFFUS_PC_Z 128
-#endif
-constexpr int kPcZ = DIFFUS_PC_Z, kPcZThin = 8, kPcCols = 9, kPcRows = 4 * kPcCols; // kPcZThin: thin sub-boxes (diffus_convert_volume_box)
-template <int PZ = kPcZ>
-__global__ __launch_bounds__(kBlock) void pair_convert_kernel(const float *__restrict__ in, float *__restrict__ out, Geom G,
-                                                              int zblk0 = 0, int byp0 = 0, int bx_0 = 0)
-{
-    __shared__ float t[kPcRows][PZ + 2];
-    // (zblk0, byp0, bx_0): the first block of a sub-box conversion (diffus_convert_volume_box); 0 for a whole volume
-    const int z0 = ((int)blockIdx.x + zblk0) * PZ;
-    const int by0 = ((int)blockIdx.y + byp0) * 2, bx = blockIdx.z + bx_0;
-    const int tid = threadIdx.x;
-    for (int e = tid; e < kPcRows * (PZ + 1); e += kBlock) {
-        int row = e / (PZ + 1), zz = e - row * (PZ + 1); // row = (x & 3) * 9 + column 0..8
-        int x = min(bx * 4 + row / kPcCols, G.d0 - 1), y = min(by0 * 4 + row % kPcCols, G.d1 - 1), z = min(z0 + zz, G.d2 - 1);
-        t[row][zz] = in[((long)x * G.d1 + y) * G.d2 + z];
-    }
-    __syncthreads();
-    // float4 = the (z, z + 1) pairs of two neighbouring columns of one x-row: 10 per record
-    constexpr int V4 = kPairFloats / 4;
-    for (int e = tid; e < 2 * PZ * V4; e += kBlock) {
-        const int half = e / (PZ * V4), r = e - half * (PZ * V4);
-        const int zz = r / V4, q = r - zz * V4;       // q-th float4 of the record: pairs 2q and 2q + 1
-        const int by = by0 + half;
-        if (by < G.nb1 && z0 + zz < G.d2) {
-            const int p0 = 2 * q, p1 = 2 * q + 1;     // pair index = (x & 3) * 5 + column
-            const int r0 = (p0 / 5) * kPcCols + half * 4 + p0 % 5, r1 = (p1 / 5) * kPcCols + half * 4 + p1 % 5;
-            const float4 v = make_float4(t[r0][zz], t[r0][zz + 1], t[r1][zz], t[r1][zz + 1]);
-            const long rec = ((long)bx * G.nb1 + by) * G.d2 + z0 + zz;
-            *reinterpret_cast<float4 *>(out + rec * kPairFloats + 4 * q) = v;
-        }
-    }
-}
-
-} // namespace
-
-extern "C" {
-
-size_t diffus_bricked_floats(int d0, int d1, int d2)
-{
-    if (d0 <= 0 || d1 <= 0 || d2 <= 0) return 0;
-    return bricked_floats(d0, d1, d2);
-}
-
-size_t diffus_brick_count(int d0, int d1, int d2)
-{
-    if (d0 <= 0 || d1 <= 0 || d2 <= 0) return 0;
-    return bricked_floats(d0, d1, d2) / kBrickFloats;
-}
-
-int diffus_gradbuf_flush(float *bricked, int *touched, int d0, int d1, int d2, float *vol, int accumulate,
-                         diffus_stream_t stream)
-{
-    if (!bricked || !touched || !vol || d0 <= 0 || d1 <= 0 || d2 <= 0) return DIFFUS_EINVAL;
-    if (accumulate < DIFFUS_FLUSH_STORE || accumulate > DIFFUS_FLUSH_DENSE) return DIFFUS_EINVAL;
-    Geom G = make_geom(d0, d1, d2);
-    const long nbricks = (long)(bricked_floats(d0, d1, d2) / kBrickFloats);
-    if (reinterpret_cast<uintptr_t>(bricked) & 15) return DIFFUS_EINVAL; // a brick is read as 16-byte words
-    const long per_wave = accumulate == DIFFUS_FLUSH_DENSE ? kWave : kFlushBricks;
-    const long waves = (nbricks + per_wave - 1) / per_wave;
-    const unsigned nblk = (unsigned)((waves + kWavesPerBlock - 1) / kWavesPerBlock);
-    if (accumulate == DIFFUS_FLUSH_DENSE)
-        hipLaunchKernelGGL(gradbuf_flush_dense_kernel, dim3(nblk), dim3(kBlock), 0, (hipStream_t)stream, bricked, touched, vol,
-                           G, nbricks);
-    else if (!(d2 & 1) && !(reinterpret_cast<uintptr_t>(vol) & 7))
-        hipLaunchKernelGGL(gradbuf_flush_kernel<true>, dim3(nblk), dim3(kBlock), 0, (hipStream_t)stream, bricked, touched, vol,
-                           G, nbricks, accumulate);
-    else
-        hipLaunchKernelGGL(gradbuf_flush_kernel<false>, dim3(nblk), dim3(kBlock), 0, (hipStream_t)stream, bricked, touched, vol,
-                           G, nbricks, accumulate);
-    return last_launch();
-}
-
-size_t diffus_paired_floats(int d0, int d1, int d2)
-{
-    if (d0 <= 0 || d1 <= 0 || d2 <= 0) return 0;
-    return paired_floats(d0, d1, d2);
-}
-
-int diffus_pair_volume(const float *vol, int d0, int d1, int d2, float *paired, diffus_stream_t stream)
-{
-    if (!vol || !paired || d0 <= 0 || d1 <= 0 || d2 <= 0) return DIFFUS_EINVAL;
-    Geom G = make_geom(d0, d1, d2);
-    dim3 grid((d2 + kPcZ - 1) / kPcZ, (G.nb1 + 1) / 2, (d0 + 3) / 4);
-    if (grid.y > 65535 || grid.z > 65535) return DIFFUS_EUNSUPPORTED;
-    hipLaunchKernelGGL(pair_convert_kernel<kPcZ>, grid, dim3(kBlock), 0, (hipStream_t)stream, vol, paired, G, 0, 0, 0);
-    return last_launch();
-}
-
-int diffus_convert_volume_box(const float *vol, int d0, int d1, int d2, int layout, float *converted, int x0, int x1,
-                              int y0, int y1, int z0, int z1, diffus_stream_t stream)
-{
-    if (!vol || !converted || d0 <= 0 || d1 <= 0 || d2 <= 0) return DIFFUS_EINVAL;
-    if (layout != DIFFUS_BRICKED && layout != DIFFUS_PAIRED) return DIFFUS_EINVAL;
-    if (x0 < 0 || y0 < 0 || z0 < 0 || x1 > d0 || y1 > d1 || z1 > d2) return DIFFUS_EINVAL;
-    if (x0 >= x1 || y0 >= y1 || z0 >= z1) return DIFFUS_OK; // an empty box
-    Geom G = make_geom(d0, d1, d2);
-    const int bx_lo = x0 >> 2, bx_hi = (x1 - 1) >> 2; // brick rows (4 voxels of dim 0): no layout repeats a dim-0 neighbour
-    // depths per block: the whole-volume kernels' (128 / 64: long coalesced rows) for a deep box, 8 for a thin one -- a
-    // slice of constant dim 2, the plane every fan of the reference lies in, is two depths of records
-    auto launch = [&](auto kernel_for, int per_block, int zlo, int zhi, int by_lo, int by_hi) { // depths zlo..zhi; by_lo..by_hi in blocks
-        const dim3 grid(zhi / per_block - zlo / per_block + 1, by_hi - by_lo + 1, bx_hi - bx_lo + 1);
-        if (grid.y > 65535 || grid.z > 65535) return (int)DIFFUS_EUNSUPPORTED;
-        kernel_for(grid, zlo / per_block, by_lo);
-        return last_launch();
-    };
-    hipStream_t st = (hipStream_t)stream;
-    if (layout == DIFFUS_PAIRED) {
-        // A record (brick column by, depth z) repeats the first column of brick column by + 1 and the depth z + 1: the
-        // records that hold a voxel of [y0, y1) x [z0, z1) are brick columns (y0 - 1) / 4 .. (y1 - 1) / 4, depths z0 - 1 .. z1 - 1
-        const int by_lo = max(y0 - 1, 0) >> 2, by_hi = (y1 - 1) >> 2, zr_lo = max(z0 - 1, 0), zr_hi = z1 - 1;
-        if (zr_hi - zr_lo < 2 * kPcZThin)
-            return launch([&](dim3 g, int zb, int byp) { hipLaunchKernelGGL(pair_convert_kernel<kPcZThin>, g, dim3(kBlock), 0, st, vol, converted, G, zb, byp, bx_lo); },
-                          kPcZThin, zr_lo, zr_hi, by_lo >> 1, by_hi >> 1);
-        return launch([&](dim3 g, int zb, int byp) { hipLaunchKernelGGL(pair_convert_kernel<kPcZ>, g, dim3(kBlock), 0, st, vol, converted, G, zb, byp, bx_lo); },
-                      kPcZ, zr_lo, zr_hi, by_lo >> 1, by_hi >> 1);
-    }
-    const int by_lo = y0 >> 2, by_hi = (y1 - 1) >> 2;
-    if (z1 - z0 <= 2 * kConvZThin)
-        return launch([&](dim3 g, int zb, int by) { hipLaunchKernelGGL((brick_convert_kernel<true, false, kConvZThin>), g, dim3(kBlock), 0, st, vol, converted, G, zb, by, bx_lo); },
-                      kConvZThin, z0, z1 - 1, by_lo, by_hi);
-    return launch([&](dim3 g, int zb, int by) { hipLaunchKernelGGL((brick_convert_kernel<true, false, kConvZ>), g, dim3(kBlock), 0, st, vol, converted, G, zb, by, bx_lo); },
-                  kConvZ, z0, z1 - 1, by_lo, by_hi);
-}
-
-int diffus_brick_volume(const float *vol, int d0, int d1, int d2, float *bricked, diffus_stream_t stream)
-{
-    if (!vol || !bricked || d0 <= 0 || d1 <= 0 || d2 <= 0) return DIFFUS_EINVAL;
-    Geom G = make_geom(d0, d1, d2);
-    dim3 grid((G.nb2 + kConvZ / 2 - 1) / (kConvZ / 2), G.nb1, (d0 + 3) / 4);
-    if (grid.y > 65535 || grid.z > 65535) return DIFFUS_EUNSUPPORTED;
-    hipLaunchKernelGGL((brick_convert_kernel<true, false>), grid, dim3(kBlock), 0, (hipStream_t)stream, vol, bricked, G, 0, 0, 0);
-    return last_launch();
-}
-
-int diffus_unbrick_volume(const float *bricked, int d0, int d1, int d2, float *vol, int accumulate,
-                          diffus_stream_t stream)
-{
-    if (!vol || !bricked || d0 <= 0 || d1 <= 0 || d2 <= 0) return DIFFUS_EINVAL;
-    Geom G = make_geom(d0, d1, d2);
-    dim3 grid((G.nb2 + kConvZ / 2 - 1) / (kConvZ / 2), G.nb1, (d0 + 3) / 4);
-    if (grid.y > 65535 || grid.z > 65535) return DIFFUS_EUNSUPPORTED;
-    if (accumulate)
-        hipLaunchKernelGGL((brick_convert_kernel<false, true>), grid, dim3(kBlock), 0, (hipStream_t)stream, bricked, vol, G, 0, 0, 0);
-    else
-        hipLaunchKernelGGL((brick_convert_kernel<false, false>), grid, dim3(kBlock), 0, (hipStream_t)stream, bricked, vol, G, 0, 0, 0);
-    return last_launch();
-}
-
 #ifdef DIFFUS_STAMP
-int diffus_debug_set_stamps(unsigned long long *p)
+extern "C" int diffus_debug_set_stamps(unsigned long long *p)
 {
     return hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), &p, sizeof(p)) == hipSuccess ? 0 : -3;
 }
 #endif
-
-} // extern "C"

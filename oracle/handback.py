@@ -1,6 +1,6 @@
 """The sparse gradient hand-back, restated in numpy.
 
-TEST INFRASTRUCTURE ONLY (oracle).  What diffus_gradbuf_flush (diffus_amd/csrc/scatter.hip: gradbuf_flush_kernel,
+TEST INFRASTRUCTURE ONLY (oracle).  What diffus_gradbuf_flush (diffus_amd/csrc/layout.hip: gradbuf_flush_kernel,
 gradbuf_flush_dense_kernel) does to the bricked gradient scratch, its touched-brick flags and the canonical tensor, so
 that multi-rank logic (diffus_amd.distributed.allreduce_touched) can be tested end to end without a GPU.
 

@@ -3,7 +3,7 @@
 issue costs MEASURED by tools/valu_issue_bench.hip (profiles/r04_valu_issue_bench.txt; cycles per wave-instruction per SIMD
 with >= 4 waves per SIMD).  Prints the opcode histogram sorted by cost and the kernel's lower bound in SIMD cycles per
 wave.  The render kernels are straight-line code with a few wave-uniform branches; -D defines pick the executed copy
-(e.g. -DDIFFUS_COUNT_PLANAR=1 -DDIFFUS_COUNT_MSE=2), so the static count is the dynamic one.
+(e.g. -DDIFFUS_COUNT_PLANAR=1 -DDIFFUS_COUNT_FAST_ONLY), so the static count is the dynamic one.
 
     tools/issue_model.py render_bwd 'render_bwd_kernel<8, 1, 2, true, 4, 0' [-DNAME=VALUE ...] [--json]
 """
