@@ -22,7 +22,9 @@ EXPORTS = ("diffus_abi_version", "diffus_strerror", "diffus_workspace_bytes", "d
            "diffus_brain_mask", "diffus_masked_stats_workspace_bytes", "diffus_masked_stats", "diffus_rows_conv1d",
            "diffus_prop_single_ray", "diffus_propagate_rays", "diffus_sample_points",
            "diffus_echo_bwd_workspace_bytes", "diffus_echo_traces_bwd", "diffus_splat_axes", "diffus_rotate_around_apex",
-           "diffus_ssim_workspace_bytes", "diffus_ssim_loss_fwd", "diffus_ssim_loss_bwd", "diffus_fan_pose_fwd", "diffus_fan_pose_bwd")
+           "diffus_ssim_workspace_bytes", "diffus_ssim_loss_fwd", "diffus_ssim_loss_bwd", "diffus_fan_pose_fwd", "diffus_fan_pose_bwd",
+           "diffus_sample_points_bwd", "diffus_trace_rays_bwd_workspace_bytes", "diffus_trace_rays_bwd",
+           "diffus_rows_conv1d_bwd_workspace_bytes", "diffus_rows_conv1d_bwd")
 
 ABI_VERSION = 8          # include/diffus_hip.h DIFFUS_ABI_VERSION
 DIFFUS_F32, DIFFUS_F64, DIFFUS_I64 = 0, 1, 2
@@ -150,6 +152,16 @@ def load():
     lib.diffus_propagate_rays.argtypes = [vp, i, i, vp, vp]
     lib.diffus_sample_points.restype = i
     lib.diffus_sample_points.argtypes = [vp, i, i, i, i, vp, C.c_long, i, vp, vp, vp]
+    lib.diffus_sample_points_bwd.restype = i
+    lib.diffus_sample_points_bwd.argtypes = [vp, i, i, i, i, vp, C.c_long, i, vp, vp, vp, vp]
+    lib.diffus_trace_rays_bwd_workspace_bytes.restype = sz
+    lib.diffus_trace_rays_bwd_workspace_bytes.argtypes = [i, i]
+    lib.diffus_trace_rays_bwd.restype = i
+    lib.diffus_trace_rays_bwd.argtypes = [vp, i, i, i, i, vp, i, vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.diffus_rows_conv1d_bwd_workspace_bytes.restype = sz
+    lib.diffus_rows_conv1d_bwd_workspace_bytes.argtypes = [i, i, i, i]
+    lib.diffus_rows_conv1d_bwd.restype = i
+    lib.diffus_rows_conv1d_bwd.argtypes = [vp, i, i, vp, i, i, vp, vp, vp, vp, sz, vp]
     if lib.diffus_abi_version() != ABI_VERSION:
         raise DiffusError("libdiffus_hip.so ABI version mismatch")
     _lib = lib

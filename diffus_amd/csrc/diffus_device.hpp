@@ -1327,24 +1327,39 @@ struct Cell {
     float t[3];
 };
 
+// axis `a` of the cell a sample at coordinate p reads: one voxel (nearest) or the two corners and the lerp fraction
+template <int SAMPLER>
+__device__ __forceinline__ void cell_axis(Cell &c, int a, float p, int dim)
+{
+    if (SAMPLER == DIFFUS_NEAREST) {
+        c.i0[a] = c.i1[a] = nearest_index(p, dim);
+        c.t[a] = 0.f;
+    } else {
+        Axis ax = tri_axis(p, dim);
+        c.i0[a] = ax.i0;
+        c.i1[a] = ax.i1;
+        c.t[a] = ax.t;
+    }
+}
+
 template <int SAMPLER, int PM = 1>
 __device__ __forceinline__ Cell cell_of(const Args &A, const Pose &ps, int k)
 {
     Cell c;
     const int dims[3] = {A.G.d0, A.G.d1, A.G.d2};
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        float p = ray_point<PM>(ps, a, k);
-        if (SAMPLER == DIFFUS_NEAREST) {
-            c.i0[a] = c.i1[a] = nearest_index(p, dims[a]);
-            c.t[a] = 0.f;
-        } else {
-            Axis ax = tri_axis(p, dims[a]);
-            c.i0[a] = ax.i0;
-            c.i1[a] = ax.i1;
-            c.t[a] = ax.t;
-        }
-    }
+    for (int a = 0; a < 3; ++a) cell_axis<SAMPLER>(c, a, ray_point<PM>(ps, a, k), dims[a]);
+    return c;
+}
+
+// ... of a sample at an arbitrary point
+template <int SAMPLER>
+__device__ __forceinline__ Cell cell_at(const Geom &G, const float (&pt)[3])
+{
+    Cell c;
+    const int dims[3] = {G.d0, G.d1, G.d2};
+#pragma unroll
+    for (int a = 0; a < 3; ++a) cell_axis<SAMPLER>(c, a, pt[a], dims[a]);
     return c;
 }
 

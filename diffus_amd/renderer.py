@@ -485,6 +485,54 @@ def _wants_grad(*tensors) -> bool:
     return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
 
 
+def _aliased_versions(pb: "_Problem", volume, sources, directions):
+    """The backward recomputes the forward from the tensors as they are THEN (nothing is stashed by value): it is only
+    right if they are unchanged, so their in-place version counters are checked like autograd checks saved tensors.
+    Checked only for the inputs the kernels will actually READ AGAIN through the caller's storage: a private copy made
+    by _Problem (device / dtype conversion, the cached bricked or paired volume) keeps the forward's values whatever the
+    caller does to the original afterwards.  -> ((name, tensor, version), ...) for _check_versions."""
+    reads_vol = pb.vol is not None and pb.layout == _lib.CANONICAL and pb.vol.data_ptr() == volume.data_ptr()
+    reads_bricked = pb.vol is None and pb.bricked.data_ptr() == volume.data_ptr()          # a BrickedVolume's own data
+    return tuple((name, t, t._version) for name, t, aliased in (
+        ("volume", volume, reads_vol or reads_bricked),
+        ("sources", sources, pb.src.data_ptr() == sources.data_ptr()),
+        ("directions", directions, pb.dirs.data_ptr() == directions.data_ptr())) if aliased)
+
+
+def _check_versions(versions):
+    for name, t, ver in versions:
+        if t._version != ver:
+            raise RuntimeError(f"diffus_amd: `{name}` was modified in place between the forward and this backward "
+                               f"(version {ver} -> {t._version}); the backward recomputes the forward from its inputs")
+
+
+def _pose_meta(volume, sources, directions):
+    return (volume.device, volume.dtype, sources.device, sources.dtype, tuple(sources.shape),
+            directions.device, directions.dtype, tuple(directions.shape))
+
+
+def _pose_grads(meta, gsrc, gdirs):
+    """(P,3) / (P,R,3) float32 pose gradients (None: not wanted) -> the caller's shapes, devices and dtypes; a fan
+    shared by all poses gets the sum over the poses."""
+    _, _, sdev, sdt, sshape, ddev, ddt, dshape = meta
+    out_s = None
+    if gsrc is not None:
+        out_s = gsrc.reshape(sshape)
+        if out_s.device != sdev or out_s.dtype != sdt:
+            out_s = out_s.to(device=sdev, dtype=sdt)
+    out_d = None
+    if gdirs is not None:
+        if len(dshape) == 3:
+            out_d = gdirs
+        elif len(dshape) == 2:      # one fan shared by all poses
+            out_d = gdirs.sum(0)
+        else:
+            out_d = gdirs.sum(0).reshape(dshape)
+        if out_d.device != ddev or out_d.dtype != ddt:
+            out_d = out_d.to(device=ddev, dtype=ddt)
+    return out_s, out_d
+
+
 class _RenderFn(torch.autograd.Function):
     """frame = render(volume, sources, directions); backward via diffus_render_bwd."""
 
@@ -493,20 +541,8 @@ class _RenderFn(torch.autograd.Function):
         pb = _Problem(volume, sources, directions, S, start, alpha, sampler, layout, shape)
         frame, idx = _forward_launch(pb, want_idx)
         ctx.pb = pb
-        # The backward recomputes the forward from the tensors as they are THEN (nothing is stashed by value): it is
-        # only right if they are unchanged, so their in-place version counters are checked like autograd checks saved
-        # tensors.
-        # Checked only for the inputs the kernels will actually READ AGAIN through the caller's storage: a private copy
-        # made above (device / dtype conversion, the cached bricked or paired volume) keeps the forward's values whatever
-        # the caller does to the original afterwards.
-        reads_vol = pb.vol is not None and pb.layout == _lib.CANONICAL and pb.vol.data_ptr() == volume.data_ptr()
-        reads_bricked = pb.vol is None and pb.bricked.data_ptr() == volume.data_ptr()          # a BrickedVolume's own data
-        ctx.versions = tuple((name, t, t._version) for name, t, aliased in (
-            ("volume", volume, reads_vol or reads_bricked),
-            ("sources", sources, pb.src.data_ptr() == sources.data_ptr()),
-            ("directions", directions, pb.dirs.data_ptr() == directions.data_ptr())) if aliased)
-        ctx.meta = (volume.device, volume.dtype, sources.device, sources.dtype, tuple(sources.shape),
-                    directions.device, directions.dtype, tuple(directions.shape))
+        ctx.versions = _aliased_versions(pb, volume, sources, directions)
+        ctx.meta = _pose_meta(volume, sources, directions)
         if idx is None:
             idx = torch.empty(0, dtype=torch.int64, device=pb.dev)
         ctx.mark_non_differentiable(idx)
@@ -517,11 +553,8 @@ class _RenderFn(torch.autograd.Function):
     def backward(ctx, gframe, _gidx):
         lib = _lib.load()
         pb = ctx.pb
-        for name, t, ver in ctx.versions:
-            if t._version != ver:
-                raise RuntimeError(f"diffus_amd: `{name}` was modified in place between the forward and this backward "
-                                   f"(version {ver} -> {t._version}); the backward recomputes the forward from its inputs")
-        vdev, vdt, sdev, sdt, sshape, ddev, ddt, dshape = ctx.meta
+        _check_versions(ctx.versions)
+        vdev, vdt = ctx.meta[:2]
         need_v, need_s, need_d = ctx.needs_input_grad[:3]
         with _Scope(pb.dev):
             g = _as(gframe, pb.dev, torch.float32)
@@ -556,21 +589,7 @@ class _RenderFn(torch.autograd.Function):
                 _lib.check(rc, "diffus_gradbuf_flush")
                 gvol = dense
         out_v = (gvol if (gvol.device == vdev and gvol.dtype == vdt) else gvol.to(device=vdev, dtype=vdt)) if need_v else None
-        out_s = None
-        if need_s:
-            out_s = gsrc.reshape(sshape)
-            if out_s.device != sdev or out_s.dtype != sdt:
-                out_s = out_s.to(device=sdev, dtype=sdt)
-        out_d = None
-        if need_d:
-            if len(dshape) == 3:
-                out_d = gdirs
-            elif len(dshape) == 2:      # one fan shared by all poses
-                out_d = gdirs.sum(0)
-            else:
-                out_d = gdirs.sum(0).reshape(dshape)
-            if out_d.device != ddev or out_d.dtype != ddt:
-                out_d = out_d.to(device=ddev, dtype=ddt)
+        out_s, out_d = _pose_grads(ctx.meta, gsrc, gdirs)
         return out_v, out_s, out_d, None, None, None, None, None, None, None
 
 
@@ -604,11 +623,9 @@ def render_poses(volume, sources, directions, num_samples, attenuation_coeff, st
     return (frame, idx) if return_indices else frame
 
 
-def trace_rays(volume, sources, directions, num_samples, sampler="nearest", want=("imp", "refl", "idx"),
-               layout="auto"):
-    """Stage 1 alone (diffus_trace_rays): -> dict with imp (P,R,S), refl (P,R,S-1), idx (3,P,R,S)."""
+def _trace_launch(pb: "_Problem", want):
+    """diffus_trace_rays on a validated problem -> (imp, refl, idx), None where not in `want`."""
     lib = _lib.load()
-    pb = _Problem(volume, sources, directions, num_samples, 0, 0.0, sampler, layout)
     with _Scope(pb.dev):
         imp = torch.empty((pb.P, pb.R, pb.S), dtype=torch.float32, device=pb.dev) if "imp" in want else None
         refl = torch.empty((pb.P, pb.R, pb.S - 1), dtype=torch.float32, device=pb.dev) if "refl" in want else None
@@ -616,6 +633,64 @@ def trace_rays(volume, sources, directions, num_samples, sampler="nearest", want
         c = pb.common()
         rc = lib.diffus_trace_rays(*c[:12], pb.sampler, _ptr(imp), _ptr(refl), _ptr(idx), _stream(pb.dev))
     _lib.check(rc, "diffus_trace_rays")
+    return imp, refl, idx
+
+
+class _TraceFn(torch.autograd.Function):
+    """(imp, refl, idx) = trace_rays(volume, sources, directions); backward via diffus_trace_rays_bwd, which samples the
+    volume again from the same (possibly converted) copy the forward read.  Outputs not asked for are empty tensors."""
+
+    @staticmethod
+    def forward(ctx, volume, sources, directions, S, sampler, want, layout):
+        pb = _Problem(volume, sources, directions, S, 0, 0.0, sampler, layout)
+        imp, refl, idx = _trace_launch(pb, want)
+        ctx.pb = pb
+        ctx.versions = _aliased_versions(pb, volume, sources, directions)
+        ctx.meta = _pose_meta(volume, sources, directions)
+        ctx.set_materialize_grads(False)
+        empty = torch.empty(0, dtype=torch.float32, device=pb.dev)
+        idx = torch.empty(0, dtype=torch.int64, device=pb.dev) if idx is None else idx
+        ctx.mark_non_differentiable(idx)
+        return (empty if imp is None else imp), (empty if refl is None else refl), idx
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gimp, grefl, _gidx):
+        lib = _lib.load()
+        pb = ctx.pb
+        _check_versions(ctx.versions)
+        vdev, vdt = ctx.meta[:2]
+        need_v, need_s, need_d = ctx.needs_input_grad[:3]
+        with _Scope(pb.dev):
+            gi = _as(gimp, pb.dev, torch.float32) if gimp is not None and gimp.numel() else None
+            gr = _as(grefl, pb.dev, torch.float32) if grefl is not None and grefl.numel() else None
+            gvol = torch.zeros(pb.shape, dtype=torch.float32, device=pb.dev) if need_v else None
+            gsrc = torch.empty((pb.P, 3), dtype=torch.float32, device=pb.dev) if need_s else None
+            gdirs = torch.empty((pb.P, pb.R, 3), dtype=torch.float32, device=pb.dev) if need_d else None
+            nws = lib.diffus_trace_rays_bwd_workspace_bytes(pb.P, pb.R) if need_s else 0
+            ws = torch.empty(nws, dtype=torch.uint8, device=pb.dev) if nws else None
+            c = pb.common()
+            rc = lib.diffus_trace_rays_bwd(*c[:12], pb.sampler, _ptr(gi), _ptr(gr), _ptr(gvol), _ptr(gsrc), _ptr(gdirs),
+                                           _ptr(ws), nws, _stream(pb.dev))
+        _lib.check(rc, "diffus_trace_rays_bwd")
+        out_v = (gvol if (gvol.device == vdev and gvol.dtype == vdt) else gvol.to(device=vdev, dtype=vdt)) if need_v else None
+        out_s, out_d = _pose_grads(ctx.meta, gsrc, gdirs)
+        return out_v, out_s, out_d, None, None, None, None
+
+
+def trace_rays(volume, sources, directions, num_samples, sampler="nearest", want=("imp", "refl", "idx"),
+               layout="auto"):
+    """Stage 1 alone (diffus_trace_rays): -> dict with imp (P,R,S), refl (P,R,S-1), idx (3,P,R,S) (None where not in
+    `want`).  Differentiable in volume (both samplers) and in sources/directions (trilinear; nearest gives them zeros,
+    as render_poses does) through diffus_trace_rays_bwd."""
+    if not _wants_grad(volume, sources, directions):
+        pb = _Problem(volume, sources, directions, num_samples, 0, 0.0, sampler, layout)
+        imp, refl, idx = _trace_launch(pb, want)
+    else:
+        imp, refl, idx = _TraceFn.apply(volume, sources, directions, num_samples, sampler, tuple(want), layout)
+        imp = imp if "imp" in want else None
+        refl = refl if "refl" in want else None
+        idx = idx if "idx" in want else None
     return {"imp": imp, "refl": refl, "idx": idx}
 
 
@@ -715,14 +790,28 @@ def custom_nearest_sampler(Z: torch.Tensor, points: torch.Tensor, visualize: boo
     """Mirror of reference src/renderer.py:741-819 for the default sampler 'prop': points (batch, num_samples, 3) in
     voxel coordinates -> (x, y, z, ray_values), each (batch, num_samples); indices are rounded half to even and
     clamped into the volume (:754-756).  `visualize` and `start` only drive the reference's matplotlib figure
-    (:762-801), which is not reproduced: they are accepted and ignored."""
-    lib = _lib.load()
+    (:762-801), which is not reproduced: they are accepted and ignored.  Differentiable in Z (both samplers) and in
+    points (trilinear) through diffus_sample_points_bwd; under nearest the points get no gradient, as in the reference."""
+    _lib.load()
     if sampler not in _SAMPLERS:
         raise ValueError(f"unknown sampler {sampler!r}")
     if Z.dim() != 3:
         raise ValueError("not enough values to unpack (expected 3, got %d)" % Z.dim())       # D, H, W = Z.shape
     if points.dim() != 3 or points.shape[-1] != 3:
         raise ValueError(f"points must be (batch, num_samples, 3); got {tuple(points.shape)}")
+    tri = _SAMPLERS[sampler] == _lib.TRILINEAR
+    if _wants_grad(Z) or (tri and _wants_grad(points)):  # nearest: the reference's .round().long() cuts the points' graph
+        vals, idx = _SampleFn.apply(Z, points, sampler)
+        return idx[0], idx[1], idx[2], vals
+    _, _, val, idx = _sample_launch(Z, points, sampler)
+    out_dev = Z.device
+    vals = val.to(device=out_dev, dtype=Z.dtype if Z.is_floating_point() else torch.float32)
+    return idx[0].to(out_dev), idx[1].to(out_dev), idx[2].to(out_dev), vals
+
+
+def _sample_launch(Z, points, sampler):
+    """diffus_sample_points -> (device volume, device points (b,ns,3) float32, values (b,ns), idx (3,b,ns)) on the GPU."""
+    lib = _lib.load()
     dev = _device_for(Z)
     vol = _as(Z, dev, torch.float32)
     pts = _as(points, dev, torch.float32)            # the reference's `points.float()` (:751)
@@ -736,9 +825,49 @@ def custom_nearest_sampler(Z: torch.Tensor, points: torch.Tensor, visualize: boo
             rc = lib.diffus_sample_points(_ptr(vol), d0, d1, d2, _lib.CANONICAL, _ptr(pts), n, _SAMPLERS[sampler], _ptr(val),
                                           _ptr(idx), _stream(dev))
             _lib.check(rc, "diffus_sample_points")
-    out_dev = Z.device
-    vals = val.to(device=out_dev, dtype=Z.dtype if Z.is_floating_point() else torch.float32)
-    return idx[0].to(out_dev), idx[1].to(out_dev), idx[2].to(out_dev), vals
+    return vol, pts, val, idx
+
+
+class _SampleFn(torch.autograd.Function):
+    """(values, idx) = custom_nearest_sampler(Z, points); backward via diffus_sample_points_bwd: d/d Z for both samplers,
+    d/d points for trilinear (None for nearest, as in the reference's graph)."""
+
+    @staticmethod
+    def forward(ctx, Z, points, sampler):
+        vol, pts, val, idx = _sample_launch(Z, points, sampler)
+        ctx.bufs = (vol, pts)
+        ctx.sampler = _SAMPLERS[sampler]
+        # the backward reads the volume and the points again: see _aliased_versions
+        ctx.versions = tuple((name, t, t._version) for name, t, buf in (("Z", Z, vol), ("points", points, pts))
+                             if buf.data_ptr() == t.data_ptr())
+        ctx.meta = (Z.device, Z.dtype, points.device, points.dtype)
+        out_dev = Z.device
+        idx = idx.to(out_dev)
+        ctx.mark_non_differentiable(idx)
+        return val.to(device=out_dev, dtype=Z.dtype if Z.is_floating_point() else torch.float32), idx
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gvals, _gidx):
+        lib = _lib.load()
+        _check_versions(ctx.versions)
+        vol, pts = ctx.bufs
+        zdev, zdt, pdev, pdt = ctx.meta
+        need_z = ctx.needs_input_grad[0]
+        need_p = ctx.needs_input_grad[1] and ctx.sampler == _lib.TRILINEAR
+        dev = vol.device
+        n = pts.shape[0] * pts.shape[1]
+        with _Scope(dev):
+            gz = torch.zeros(vol.shape, dtype=torch.float32, device=dev) if need_z else None
+            gp = torch.zeros(pts.shape, dtype=torch.float32, device=dev) if need_p else None
+            if n and (need_z or need_p):
+                g = _as(gvals, dev, torch.float32)
+                rc = lib.diffus_sample_points_bwd(_ptr(vol), *vol.shape, _lib.CANONICAL, _ptr(pts), n, ctx.sampler, _ptr(g),
+                                                  _ptr(gz), _ptr(gp), _stream(dev))
+                _lib.check(rc, "diffus_sample_points_bwd")
+        out_z = gz.to(device=zdev, dtype=zdt) if need_z else None
+        out_p = gp.to(device=pdev, dtype=pdt) if need_p else None
+        return out_z, out_p, None
 
 
 def gaussian_pulse(length: int, sigma: float):
@@ -755,22 +884,70 @@ def compute_gaussian_pulse(refLR: torch.Tensor, spacing: float = 1.0, c: float =
     """Echo series of every ray passed through the transducer pulse (reference src/renderer.py:459-479): echo traces
     by diffus_echo_traces, then each row correlated with the pulse (`length` taps, `length // 2` zeros of padding on
     both sides, like the F.conv1d at :477) by diffus_rows_conv1d.  `pulse` may be given as a (1,1,L) tensor like the
-    reference's; the default is gaussian_pulse(length, sigma)."""
-    lib = _lib.load()
+    reference's; the default is gaussian_pulse(length, sigma).  Differentiable in refLR and in a `pulse` tensor
+    (diffus_echo_traces_bwd, diffus_rows_conv1d_bwd)."""
+    _lib.load()
     echo, _ = compute_echo_traces(refLR, spacing, c)
-    dev = echo.device if echo.is_cuda else _device_for(echo)
     taps = gaussian_pulse(length=length, sigma=sigma) if pulse is None else pulse
+    if _wants_grad(echo, taps):
+        return _PulseFn.apply(echo, taps, length // 2)
+    return _pulse_launch(echo, taps, length // 2)[0]
+
+
+def _pulse_launch(echo, taps, pad):
+    """diffus_rows_conv1d of every echo row with the taps -> (out on echo's device, device echo, device taps)."""
+    lib = _lib.load()
+    dev = echo.device if echo.is_cuda else _device_for(echo)
     taps = _as(torch.as_tensor(taps, dtype=torch.float32).reshape(-1), dev, torch.float32)
     e = _as(echo, dev, torch.float32)
     B, N = e.shape
-    L, pad = int(taps.numel()), length // 2
+    L = int(taps.numel())
     M = N + 2 * pad - L + 1
     if M <= 0:
         raise RuntimeError("Kernel size can't be greater than actual input size")     # what F.conv1d raises
     with _Scope(dev):
         out = torch.empty((B, M), dtype=torch.float32, device=dev)
         _lib.check(lib.diffus_rows_conv1d(_ptr(e), B, N, _ptr(taps), L, pad, _ptr(out), _stream(dev)), "diffus_rows_conv1d")
-    return out.to(echo.device)
+    return out.to(echo.device), e, taps
+
+
+class _PulseFn(torch.autograd.Function):
+    """out = rows_conv1d(echo, pulse); backward via diffus_rows_conv1d_bwd (d/d echo: the transposed correlation; d/d pulse:
+    fixed-order block partials, bitwise repeatable)."""
+
+    @staticmethod
+    def forward(ctx, echo, taps, pad):
+        out, e, k = _pulse_launch(echo, taps, pad)
+        ctx.save_for_backward(e, k)       # torch raises if either is the caller's tensor and is edited in place
+        ctx.pad = pad
+        ctx.meta = (echo.device, echo.dtype)
+        ctx.tmeta = (taps.device, taps.dtype, tuple(taps.shape)) if isinstance(taps, torch.Tensor) else None
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        lib = _lib.load()
+        e, k = ctx.saved_tensors
+        dev = e.device
+        B, N = e.shape
+        L = int(k.numel())
+        need_e = ctx.needs_input_grad[0]
+        need_k = ctx.needs_input_grad[1]
+        with _Scope(dev):
+            g = _as(gout, dev, torch.float32)
+            gin = torch.empty((B, N), dtype=torch.float32, device=dev) if need_e else None
+            gk = torch.empty(L, dtype=torch.float32, device=dev) if need_k else None
+            nws = lib.diffus_rows_conv1d_bwd_workspace_bytes(B, N, L, ctx.pad) if need_k else 0
+            ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
+            _lib.check(lib.diffus_rows_conv1d_bwd(_ptr(e), B, N, _ptr(k), L, ctx.pad, _ptr(g), _ptr(gin), _ptr(gk), _ptr(ws),
+                                                  nws, _stream(dev)), "diffus_rows_conv1d_bwd")
+        out_e = gin.to(device=ctx.meta[0], dtype=ctx.meta[1]) if need_e else None
+        out_k = None
+        if need_k:
+            tdev, tdt, tshape = ctx.tmeta
+            out_k = gk.reshape(tshape).to(device=tdev, dtype=tdt)
+        return out_e, out_k, None
 
 
 class UltrasoundRenderer:

@@ -329,6 +329,46 @@ int diffus_rows_conv1d(const float *in, int B, int N, const float *kernel, int L
                        diffus_stream_t stream);
 
 /*
+ * Backward of the stage-level functions above, which the reference differentiates by composing them by hand
+ * (custom_nearest_sampler -> compute_reflection_coeff -> compute_echo_traces).  The volume gradient
+ * `gvol` is always a CANONICAL (d0,d1,d2) float32 buffer that the call ADDS into (the caller zeroes it), whatever
+ * layout `vol` is read in; every output pointer is nullable.  Pose and pulse gradients are fixed-order sums (bitwise
+ * repeatable); volume gradients are float atomics.
+ *
+ * diffus_sample_points_bwd: custom_nearest_sampler (reference src/renderer.py:741-759; vals = Z[x,y,z] at :758) at
+ *   points (n,3) float32, gvalues (n) = d loss / d values -> gvol; gpoints (n,3) = gvalue * grad v(p) with the
+ *   trilinear border rule (no gradient along an axis where p <= 0 or p >= dim - 1), zeros for nearest (the
+ *   reference's .round().long() at :754-756 passes nothing).
+ */
+int diffus_sample_points_bwd(const float *vol, int d0, int d1, int d2, int layout, const float *points, long n, int sampler,
+                             const float *gvalues, float *gvol, float *gpoints, diffus_stream_t stream);
+
+/*
+ * diffus_trace_rays_bwd: trace_ray / simulate_rays (reference src/renderer.py:90-180, :35-71, reflection :27-33 and
+ *   :65-68) as diffus_trace_rays evaluates them.  gimp (P,R,S) = d loss / d imp, grefl (P,R,S-1) = d loss / d refl,
+ *   either NULL.  A sample's impedance gradient gimp[k] + the two reflection terms (r = (Z2-Z1)/(Z1+Z2); float32
+ *   operands as torch's DivBackward, so Z1 + Z2 = 0 gives its inf / NaN) goes to gvol (one voxel, or eight corners)
+ *   and, trilinear only, to the pose: gsrc (P,3) = sum_{r,k} gz grad v(p_k), gdirs (P,R,3) = sum_k k gz grad v(p_k),
+ *   float32 whatever src_dtype / dirs_dtype are.  Nearest writes zeros to gsrc / gdirs.  `workspace`:
+ *   diffus_trace_rays_bwd_workspace_bytes(P, R) bytes, needed when gsrc is set (trilinear), else may be NULL.
+ */
+size_t diffus_trace_rays_bwd_workspace_bytes(int P, int R);
+int diffus_trace_rays_bwd(const float *vol, int d0, int d1, int d2, int layout, const void *src, int src_dtype,
+                          const void *dirs, int dirs_dtype, int P, int R, int S, int sampler, const float *gimp,
+                          const float *grefl, float *gvol, float *gsrc, float *gdirs, void *workspace,
+                          size_t workspace_bytes, diffus_stream_t stream);
+
+/*
+ * diffus_rows_conv1d_bwd: the pulse stage of compute_gaussian_pulse (reference src/renderer.py:459-479, F.conv1d at
+ *   :477).  gout (B, N + 2*pad - L + 1) -> gin (B,N) = the transposed correlation (overwritten), gkernel (L) =
+ *   sum_{b,m} gout[b,m] in[b,m+t-pad] (overwritten; float64 inside, fixed-order per-block partials).  `workspace`:
+ *   diffus_rows_conv1d_bwd_workspace_bytes(B, N, L, pad) bytes, needed when gkernel is set.
+ */
+size_t diffus_rows_conv1d_bwd_workspace_bytes(int B, int N, int L, int pad);
+int diffus_rows_conv1d_bwd(const float *in, int B, int N, const float *kernel, int L, int pad, const float *gout, float *gin,
+                           float *gkernel, void *workspace, size_t workspace_bytes, diffus_stream_t stream);
+
+/*
  * Scan conversion (the step after the path): replaces
  * differentiable_splat (reference src/renderer.py:694-737) for P frames at once.
  *   c0, c1  (P,n) float32: the two plotted coordinates of every sample (the
