@@ -17,8 +17,9 @@ from .impedance import ImpedanceEstimator, create_brain_mask, masked_stats, zsco
 from .captured import CapturedStep  # noqa: F401,E402
 from .losses import ssim_loss  # noqa: F401,E402
 from .raster import rasterize_fan  # noqa: F401,E402
+from .probes import ArrayPose, convex_array, linear_array  # noqa: F401,E402
 
-__all__ = ["ssim_loss", "rasterize_fan", "prop_single_ray", "propagate_full_rays_batched", "custom_nearest_sampler", "CapturedStep", "ImpedanceEstimator", "create_brain_mask", "zscore_normalize", "masked_stats", "apply_artifacts", "artifact_noise", "compute_gaussian_pulse", "gaussian_pulse", "FanPose", "compute_us_apex_and_direction", "cone_us_to_mri_world", "voxel_to_world", "world_to_voxel", "mri_to_us_point", "us_to_mri_point", "rotation_from_rotvec",
+__all__ = ["ArrayPose", "linear_array", "convex_array", "ssim_loss", "rasterize_fan", "prop_single_ray", "propagate_full_rays_batched", "custom_nearest_sampler", "CapturedStep", "ImpedanceEstimator", "create_brain_mask", "zscore_normalize", "masked_stats", "apply_artifacts", "artifact_noise", "compute_gaussian_pulse", "gaussian_pulse", "FanPose", "compute_us_apex_and_direction", "cone_us_to_mri_world", "voxel_to_world", "world_to_voxel", "mri_to_us_point", "us_to_mri_point", "rotation_from_rotvec",
            "differentiable_splat", "rotate_around_apex", "splat_frames", "UltrasoundRenderer", "compute_echo_traces", "render_poses", "trace_rays", "resolve_start",
            "generate_cone_directions", "fan_directions", "fan_directions_torch", "DiffusError", "BrickedVolume", "brick_volume",
            "unbrick_volume", "pair_volume"]

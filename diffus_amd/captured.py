@@ -165,10 +165,14 @@ class CapturedStep:
         self.dev = dev
         self.vol = volume
         self.dims = tuple(int(x) for x in volume.shape)
-        self.src = _pose_tensor(sources, dev).reshape(-1, 3)
+        # sources (P,3): one apex per pose; (P,R,3): one origin per ray (DIFFUS_SRC_PER_RAY), gsrc then (P,R,3) too
+        self.per_ray = sources.dim() == 3
+        self.src = _pose_tensor(sources, dev) if self.per_ray else _pose_tensor(sources, dev).reshape(-1, 3)
         self.dirs = _pose_tensor(directions, dev)
         if self.dirs.dim() != 3 or self.dirs.shape[0] != self.src.shape[0] or self.dirs.shape[2] != 3:
             raise ValueError(f"directions must be (P,R,3) with P = {self.src.shape[0]}; got {tuple(self.dirs.shape)}")
+        if self.per_ray and self.src.shape != self.dirs.shape:
+            raise ValueError(f"per-ray sources must have the shape of directions; got {tuple(self.src.shape)}, {tuple(self.dirs.shape)}")
         self.layout = _LAYOUT_ID[layout]
         self.sampler = _SAMPLER_ID[sampler]
         # fans: "planar" -- the caller vouches that no ray moves along dim 2 (every fan of the reference: src/cone.py:258): the
@@ -182,7 +186,8 @@ class CapturedStep:
         if fans not in ("auto", "planar", "oblique"):
             raise ValueError("fans: 'auto', 'planar' or 'oblique'")
         self.fans = fans
-        self._planar = (fans == "planar") or (fans == "auto" and bool((self.dirs[..., 2] == 0).all()))
+        self._planar = (fans == "planar") or (fans == "auto" and bool((self.dirs[..., 2] == 0).all()) and
+                                              (not self.per_ray or bool((self.src[..., 2] == self.src[..., :1, 2]).all())))
         self.P, self.R = self.dirs.shape[0], self.dirs.shape[1]
         self.S, self.start, self.alpha = int(num_samples), int(start), float(attenuation_coeff)
         self.N1 = self.S - self.start
@@ -254,13 +259,13 @@ class CapturedStep:
         # nearest sampling has no pose gradient (integer indices, reference :754-758): the two tensors are zero once and
         # for all and are not handed to the library, which would otherwise memset them in every step
         self._pose_grads = self.sampler == _lib.TRILINEAR
-        self.gsrc = (torch.empty if self._pose_grads else torch.zeros)((self.P, 3), dtype=torch.float32, device=dev)
+        self.gsrc = (torch.empty if self._pose_grads else torch.zeros)(self.src.shape, dtype=torch.float32, device=dev)
         self.gdirs = (torch.empty if self._pose_grads else torch.zeros)((self.P, self.R, 3), dtype=torch.float32, device=dev)
         self.loss = torch.empty((self.P,), dtype=torch.float32, device=dev)
         self.loss_ws = torch.zeros(max(512 * self.P, 512), dtype=torch.uint8, device=dev)   # arrival counters: zero once
         nws = max(self.lib.diffus_workspace_bytes(self.P, self.R, self.S, self.start), 256)
         self.ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-        sdt = _lib.DIFFUS_F64 if self.src.dtype == torch.float64 else _lib.DIFFUS_F32
+        sdt = (_lib.DIFFUS_F64 if self.src.dtype == torch.float64 else _lib.DIFFUS_F32) | (_lib.SRC_PER_RAY if self.per_ray else 0)
         ddt = _lib.DIFFUS_F64 if self.dirs.dtype == torch.float64 else _lib.DIFFUS_F32
         # every pointer below is fixed for the life of the object (inputs are updated in place)
         self.common = (_vp(self.vol_k), d0, d1, d2, self.layout, _vp(self.src), sdt, _vp(self.dirs), ddt, self.P, self.R,
@@ -295,6 +300,8 @@ class CapturedStep:
 
     def set_poses(self, sources: torch.Tensor, directions: Optional[torch.Tensor] = None):
         self.src.copy_(sources.reshape(self.src.shape))
+        if self.per_ray:
+            self._directions_changed()  # per-ray origins may leave the slice too (the hint only; the scatter checks on the device)
         if directions is not None:
             self.dirs.copy_(directions.reshape(self.dirs.shape))
             self._directions_changed()
@@ -561,6 +568,8 @@ class CapturedStep:
                 self._stamp += 1
             if s.data_ptr() != self.src.data_ptr():
                 self.src.copy_(s.reshape(self.src.shape))
+                if self.per_ray:
+                    self._directions_changed()
                 self._stamp += 1
             if d.data_ptr() != self.dirs.data_ptr():
                 self.dirs.copy_(d.reshape(self.dirs.shape))

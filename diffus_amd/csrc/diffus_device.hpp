@@ -26,6 +26,7 @@
 // gets its own copy and nothing here has external linkage.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include <type_traits>
@@ -312,14 +313,17 @@ struct Pose {
 
 // PM = 0: both inputs are f32 (the common case) -- compile-time: no f64 code, no mode branches.
 // PM = 1: dtypes resolved at run time.
+// PM = 2, 3: the same with one source per RAY (DIFFUS_SRC_PER_RAY: src is (P,R,3), read at the ray's linear index).
+// Bit 0 of PM is "dtypes at run time", bit 1 "per-ray source"; every PM test below looks at one of the two bits.
 template <int PM = 1>
 __device__ __forceinline__ void load_pose(Pose &ps, const void *src, int src_f64, const void *dirs, int dir_f64,
                                           long pose, long ray_lin)
 {
-    if (PM == 0) {
+    const long si = (PM & 2) ? ray_lin : pose;
+    if ((PM & 1) == 0) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            ps.sf[c] = ((const float *)src)[pose * 3 + c];
+            ps.sf[c] = ((const float *)src)[si * 3 + c];
             ps.df[c] = ((const float *)dirs)[ray_lin * 3 + c];
         }
         ps.pmode = 0;
@@ -327,10 +331,10 @@ __device__ __forceinline__ void load_pose(Pose &ps, const void *src, int src_f64
     }
     for (int c = 0; c < 3; ++c) {
         if (src_f64) {
-            ps.sd[c] = ((const double *)src)[pose * 3 + c];
+            ps.sd[c] = ((const double *)src)[si * 3 + c];
             ps.sf[c] = (float)ps.sd[c];
         } else {
-            ps.sf[c] = ((const float *)src)[pose * 3 + c];
+            ps.sf[c] = ((const float *)src)[si * 3 + c];
             ps.sd[c] = (double)ps.sf[c];
         }
         if (dir_f64) {
@@ -349,7 +353,7 @@ __device__ __forceinline__ void load_pose(Pose &ps, const void *src, int src_f64
 template <int PM = 1>
 __device__ __forceinline__ float ray_point_f(const Pose &ps, int c, float stepf) // stepf = float(k), exact below 2^24
 {
-    if (PM == 0 || ps.pmode == 0) {
+    if ((PM & 1) == 0 || ps.pmode == 0) {
         return __fadd_rn(ps.sf[c], __fmul_rn(stepf, ps.df[c]));
     } else if (ps.pmode == 1) {
         float t = __fmul_rn(stepf, ps.df[c]);
@@ -362,7 +366,7 @@ template <int PM = 1>
 __device__ __forceinline__ float ray_point(const Pose &ps, int c, int k)
 {
     float stepf = (float)k;
-    if (PM == 0 || ps.pmode == 0) {
+    if ((PM & 1) == 0 || ps.pmode == 0) {
         return __fadd_rn(ps.sf[c], __fmul_rn(stepf, ps.df[c]));
     } else if (ps.pmode == 1) {
         float t = __fmul_rn(stepf, ps.df[c]);
@@ -585,6 +589,7 @@ struct Args {
     // launch per segment, chained through per-ray carries in the workspace: [seg0, seg0+segN) is the
     // segment of this launch (seg0 = 0, segN = N1 when the ray fits one launch).
     int seg0, segN;
+    int src_per_ray;   // DIFFUS_SRC_PER_RAY: src is (P,R,3), kernels with bit 1 of PM set (in the padding before cin: no offset moves)
     const float *cin;  // nullable (P*R,5): running product P (normalised) + impedance of sample seg0-1
     float *cout;       // nullable (P*R,5): the same after this segment's last sample
     const float *cnext; // backward, nullable (P*R,5): carry-in of the NEXT segment (= cout of the carry-only pass)
@@ -627,6 +632,7 @@ struct Args {
                     // trilinear, their spatial gradients -- all the backward needs to route d/d median (no re-sampling)
 };
 } // namespace diffus
+static_assert(offsetof(diffus::Args, src_per_ray) % 8 == 4, "src_per_ray fills the padding in front of a pointer: the layout is unchanged");
 using diffus::Args;
 namespace {
 
@@ -1034,7 +1040,7 @@ __device__ __forceinline__ void gather_interleaved(const Args &A, int seg0, int 
 #ifdef DIFFUS_COUNT_PLANAR // tools/kernel_resources.py -DDIFFUS_COUNT_PLANAR=1|0: static count of ONE of the two copies
     const bool planar = DIFFUS_COUNT_PLANAR;
 #else
-    const bool planar = (PM == 0 || ps.pmode != 2) ? (ps.df[2] == 0.f) : (ps.dd[2] == 0.0);
+    const bool planar = ((PM & 1) == 0 || ps.pmode != 2) ? (ps.df[2] == 0.f) : (ps.dd[2] == 0.0);
 #endif
     if (planar)
         gather_interleaved_z<C, SAMPLER, LAYOUT, GRAD, PM, true>(A, seg0, segN, ps, lane, z, g0, g1, g2);
@@ -1421,13 +1427,13 @@ __device__ __forceinline__ float sample_rt(const Args &A, const Pose &ps, int k)
     const float q0 = __fadd_rn(c00, __fmul_rn(b.t, f0)), q1 = __fadd_rn(c10, __fmul_rn(b.t, f1));
     return __fadd_rn(q0, __fmul_rn(a.t, q1 - q0));
 }
-template <int SAMPLER, int C> // C samples per lane: 64 C >= N1 (8 for rays of up to 512 samples: half the serial chain of 16)
+template <int SAMPLER, int C, bool PR> // C samples per lane: 64 C >= N1 (8 for rays of up to 512 samples: half the serial chain of 16)
 __device__ __forceinline__ void repair_ray_f64(const Args &A, long pose, long w, float *zbuf)
 {
     const int lane = threadIdx.x & 63;
     const int N1 = A.N1, n0 = lane * C;
     Pose ps;
-    load_pose(ps, A.src, A.src_f64, A.dirs, A.dir_f64, pose, w);
+    load_pose<PR ? 3 : 1>(ps, A.src, A.src_f64, A.dirs, A.dir_f64, pose, w);
     const float medv = (A.start > 0) ? A.med[pose] : 0.f;
     // samples, INTERLEAVED (n = i 64 + lane), four in flight
 #pragma unroll 4
@@ -1501,9 +1507,11 @@ __device__ __forceinline__ void repair_ray_f64(const Args &A, long pose, long w,
 //     ray that supplied the median.  Its two samples and their spatial gradients wait in medinfo (median_kernel), so
 //     nothing is sampled again: d r / d Z -> volume gradient (8 corner atomics per sample), d/d source and d/d direction
 //     of that ray;
-//   * d/d source[pose] = fixed-order sum over rays of the per-ray partials (+ the median ray's extra term).
+//   * d/d source[pose] = fixed-order sum over rays of the per-ray partials (+ the median ray's extra term).  PR (per-ray
+//     sources, DIFFUS_SRC_PER_RAY): no sum -- the partials are copied to d/d source[pose, ray], the median ray's term added
+//     to that ray's entry.
 // GLAYOUT is the GRADIENT layout.  sm: 3 * kBlock floats; REPAIR: (blockDim.x / 64) * DIFFUS_MAX_SAMPLES (a row of samples per wave).
-template <int SAMPLER, int GLAYOUT, bool REPAIR>
+template <int SAMPLER, int GLAYOUT, bool REPAIR, bool PR>
 __device__ __forceinline__ void pose_finish_block(const Args &A, int pose, float *sm)
 {
     // every sum of the epilogue at once: d/dsource partials (3), loss partials, the median's gradient shares; all loads
@@ -1527,8 +1535,8 @@ __device__ __forceinline__ void pose_finish_block(const Args &A, int pose, float
                 if (seen++ % nw == wib) {
                     const long wr = (long)pose * A.R + base + b;
                     float *zbuf = sm + wib * DIFFUS_MAX_SAMPLES;
-                    if (A.N1 <= 8 * kWave) repair_ray_f64<SAMPLER, 8>(A, pose, wr, zbuf);
-                    else repair_ray_f64<SAMPLER, DIFFUS_MAX_SAMPLES / kWave>(A, pose, wr, zbuf);
+                    if (A.N1 <= 8 * kWave) repair_ray_f64<SAMPLER, 8, PR>(A, pose, wr, zbuf);
+                    else repair_ray_f64<SAMPLER, DIFFUS_MAX_SAMPLES / kWave, PR>(A, pose, wr, zbuf);
                 }
             }
         }
@@ -1537,7 +1545,12 @@ __device__ __forceinline__ void pose_finish_block(const Args &A, int pose, float
     if (A.gsrc_out)
         for (int i = tid; i < A.R; i += nt) {
             const float *q = A.gsrc_part + ((long)pose * A.R + i) * 3;
-            a[0] += q[0]; a[1] += q[1]; a[2] += q[2];
+            if (PR) {
+                float *o = A.gsrc_out + ((long)pose * A.R + i) * 3; // read by thread 0 below, after block_sums' barrier
+                o[0] = q[0]; o[1] = q[1]; o[2] = q[2];
+            } else {
+                a[0] += q[0]; a[1] += q[1]; a[2] += q[2];
+            }
         }
     if (A.loss_out)
         for (int i = tid; i < 2 * A.R; i += nt) a[3] += A.loss_part[(long)pose * 2 * A.R + i];
@@ -1552,7 +1565,7 @@ __device__ __forceinline__ void pose_finish_block(const Args &A, int pose, float
             if (i >= 0 && gm != 0.f && finitef(gm)) {
                 const long w = (long)pose * A.R + i;
                 Pose ps;
-                load_pose(ps, A.src, A.src_f64, A.dirs, A.dir_f64, pose, w);
+                load_pose<PR ? 3 : 1>(ps, A.src, A.src_f64, A.dirs, A.dir_f64, pose, w);
                 const float *mi = A.medinfo + (long)pose * 8;
                 const float z0 = mi[0], z1 = mi[1];
                 const float inv = __fdiv_rn(1.f, z0 + z1);
@@ -1582,9 +1595,11 @@ __device__ __forceinline__ void pose_finish_block(const Args &A, int pose, float
                 }
                 if (SAMPLER == DIFFUS_TRILINEAR && A.gdirs)
                     for (int c = 0; c < 3; ++c) A.gdirs[w * 3 + c] += gd[c]; // this block is the only writer now
+                if (PR && SAMPLER == DIFFUS_TRILINEAR && A.gsrc_out)
+                    for (int c = 0; c < 3; ++c) A.gsrc_out[w * 3 + c] += gs[c];
             }
         }
-        if (A.gsrc_out)
+        if (A.gsrc_out && !PR)
             for (int c = 0; c < 3; ++c) A.gsrc_out[pose * 3 + c] = a[c] + gs[c];
         if (A.loss_out) A.loss_out[pose] = a[3];
     }

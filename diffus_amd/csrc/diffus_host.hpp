@@ -102,7 +102,8 @@ int check_common(const float *vol, int d0, int d1, int d2, const void *src, int 
 {
     if (!vol || !src || !dirs) return DIFFUS_EINVAL;
     if (d0 <= 0 || d1 <= 0 || d2 <= 0 || P <= 0 || R <= 0 || S <= 0) return DIFFUS_EINVAL;
-    if ((src_dtype != DIFFUS_F32 && src_dtype != DIFFUS_F64) || (dirs_dtype != DIFFUS_F32 && dirs_dtype != DIFFUS_F64))
+    const int sdt = src_dtype & ~DIFFUS_SRC_PER_RAY; // src (P,R,3) instead of (P,3): the flag bit, then the dtype
+    if ((sdt != DIFFUS_F32 && sdt != DIFFUS_F64) || (dirs_dtype != DIFFUS_F32 && dirs_dtype != DIFFUS_F64))
         return DIFFUS_EINVAL;
     if (sampler != DIFFUS_NEAREST && sampler != DIFFUS_TRILINEAR) return DIFFUS_EINVAL;
     if (layout != DIFFUS_CANONICAL && layout != DIFFUS_BRICKED && layout != DIFFUS_PAIRED) return DIFFUS_EINVAL;
@@ -126,7 +127,8 @@ Args make_args(const float *vol, int d0, int d1, int d2, int layout, const void 
     A.vol = vol;
     A.G = make_geom(d0, d1, d2, layout);
     A.src = src; A.dirs = dirs;
-    A.src_f64 = src_dtype == DIFFUS_F64; A.dir_f64 = dirs_dtype == DIFFUS_F64;
+    A.src_f64 = (src_dtype & ~DIFFUS_SRC_PER_RAY) == DIFFUS_F64; A.dir_f64 = dirs_dtype == DIFFUS_F64;
+    A.src_per_ray = (src_dtype & DIFFUS_SRC_PER_RAY) != 0;
     A.P = P; A.R = R; A.S = S; A.start = start; A.N1 = S - start;
     A.seg0 = 0; A.segN = A.N1; // one launch covers the ray unless the caller loops over segments
     A.neg_alpha = -alpha;
@@ -147,6 +149,19 @@ int dispatch_layout(int layout, F &&f)
     case DIFFUS_CANONICAL: return f(S_{}, std::integral_constant<int, DIFFUS_CANONICAL>{});
     case DIFFUS_BRICKED: return f(S_{}, std::integral_constant<int, DIFFUS_BRICKED>{});
     default: return f(S_{}, std::integral_constant<int, DIFFUS_PAIRED>{});
+    }
+}
+
+// (dtypes, per-ray sources) -> the PM template argument of load_pose (diffus_device.hpp)
+template <typename F>
+int dispatch_pm(const Args &A, F &&f)
+{
+    const int pm = ((A.src_f64 || A.dir_f64) ? 1 : 0) | (A.src_per_ray ? 2 : 0);
+    switch (pm) {
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    default: return f(std::integral_constant<int, 3>{});
     }
 }
 

@@ -613,11 +613,11 @@ __global__ __launch_bounds__(kWave *WPB, (SPLIT > 1 ? DIFFUS_SPLIT_MIN_WAVES : (
 }
 
 // One block per pose: what pose_finish_block does, as a launch of its own (no scatter launch to ride on).
-template <int SAMPLER, int GLAYOUT>
+template <int SAMPLER, int GLAYOUT, bool PR>
 __global__ __launch_bounds__(kBlock) void pose_finish_kernel(Args A)
 {
     __shared__ float sm[kWavesPerBlock * DIFFUS_MAX_SAMPLES];
-    pose_finish_block<SAMPLER, GLAYOUT, true>(A, blockIdx.x, sm);
+    pose_finish_block<SAMPLER, GLAYOUT, true, PR>(A, blockIdx.x, sm);
 }
 
 template <int SM, int LY, bool GPOSE, int PM>
@@ -660,7 +660,7 @@ int launch_bwd_p(const Args &A, hipStream_t st)
 template <int SM, int LY, bool GPOSE>
 int launch_bwd_t(const Args &A, hipStream_t st)
 {
-    return (!A.src_f64 && !A.dir_f64) ? launch_bwd_p<SM, LY, GPOSE, 0>(A, st) : launch_bwd_p<SM, LY, GPOSE, 1>(A, st);
+    return dispatch_pm(A, [&](auto P_) { return launch_bwd_p<SM, LY, GPOSE, decltype(P_)::value>(A, st); });
 }
 
 int launch_bwd(const Args &A, int sampler, int layout, bool pose, hipStream_t st)
@@ -699,7 +699,8 @@ int render_bwd_impl(const float *vol, int d0, int d1, int d2, int layout, const 
     hipStream_t st = (hipStream_t)stream;
     const bool pose = sampler == DIFFUS_TRILINEAR && (gsrc || gdirs);
     if (sampler == DIFFUS_NEAREST && do_scan) { // integer indices: no pose gradient (reference :754-758)
-        if (gsrc && hipMemsetAsync(gsrc, 0, sizeof(float) * (size_t)P * 3, st) != hipSuccess) return DIFFUS_ELAUNCH;
+        const size_t nsrc = (src_dtype & DIFFUS_SRC_PER_RAY) ? (size_t)P * R : (size_t)P;
+        if (gsrc && hipMemsetAsync(gsrc, 0, sizeof(float) * nsrc * 3, st) != hipSuccess) return DIFFUS_ELAUNCH;
         if (gdirs && hipMemsetAsync(gdirs, 0, sizeof(float) * (size_t)P * R * 3, st) != hipSuccess) return DIFFUS_ELAUNCH;
     }
     if (sampler == DIFFUS_NEAREST && !gvol && !(mse && loss) && !(mse == 2 && frame_out)) return DIFFUS_OK;
@@ -773,7 +774,10 @@ int render_bwd_impl(const float *vol, int d0, int d1, int d2, int layout, const 
     if (finish && !A.finish_in_scatter) {
         rc = dispatch_sl(sampler, glayout, [&](auto S_, auto L_) {
             constexpr int GL = (decltype(L_)::value == DIFFUS_PAIRED) ? DIFFUS_BRICKED : decltype(L_)::value;
-            hipLaunchKernelGGL((pose_finish_kernel<decltype(S_)::value, GL>), dim3(P), dim3(kBlock), 0, st, A);
+            if (A.src_per_ray)
+                hipLaunchKernelGGL((pose_finish_kernel<decltype(S_)::value, GL, true>), dim3(P), dim3(kBlock), 0, st, A);
+            else
+                hipLaunchKernelGGL((pose_finish_kernel<decltype(S_)::value, GL, false>), dim3(P), dim3(kBlock), 0, st, A);
             return last_launch();
         });
         if (rc) return rc;

@@ -111,7 +111,7 @@ __global__ __launch_bounds__(kWave *WPB, (C <= 8 ? DIFFUS_FWD_MIN_WAVES : 1)) vo
 
 // trace_ray + custom_nearest_sampler + compute_reflection_coeff
 // (reference src/renderer.py:90-180, :741-759, :27-33, :65-68): one thread per sample.
-template <int SAMPLER, int LAYOUT>
+template <int SAMPLER, int LAYOUT, bool PR>
 __global__ __launch_bounds__(kBlock) void trace_rays_kernel(Args A, float *__restrict__ imp, float *__restrict__ refl,
                                                             long long *__restrict__ idx)
 {
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(kBlock) void trace_rays_kernel(Args A, float *__res
         const long w = t / A.S;
         const int k = (int)(t - w * A.S);
         Pose ps;
-        load_pose(ps, A.src, A.src_f64, A.dirs, A.dir_f64, w / A.R, w);
+        load_pose<PR ? 3 : 1>(ps, A.src, A.src_f64, A.dirs, A.dir_f64, w / A.R, w);
         float zz[2];
         const int nq = (refl && k + 1 < A.S) ? 2 : 1;
         for (int q = 0; q < nq; ++q) {
@@ -401,7 +401,7 @@ __global__ __launch_bounds__(kBlock) void render_fwd_long_repair_kernel(Args A)
 // ----------------------------------------------------------------------------
 // start > 0: median over rays of r[:, start] (reference :243), one block per pose.
 // Lower median like torch.median; NaN if any NaN.  Leaves the median ray's samples in medinfo for the backward.
-template <int SAMPLER, int LAYOUT>
+template <int SAMPLER, int LAYOUT, bool PR>
 __global__ __launch_bounds__(kBlock) void median_kernel(Args A)
 {
     extern __shared__ __attribute__((aligned(16))) float vals[];
@@ -412,7 +412,7 @@ __global__ __launch_bounds__(kBlock) void median_kernel(Args A)
     // the two samples (steps start, start + 1) of a ray and, trilinear, their spatial gradients: mi[8] as in medinfo
     auto sample_ray = [&](int i, float (&mi)[8]) {
         Pose ps;
-        load_pose(ps, A.src, A.src_f64, A.dirs, A.dir_f64, pose, (long)pose * A.R + i);
+        load_pose<PR ? 3 : 1>(ps, A.src, A.src_f64, A.dirs, A.dir_f64, pose, (long)pose * A.R + i);
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const int k = A.start + q;
@@ -525,11 +525,12 @@ int launch_fwd_seg(const Args &A, hipStream_t st)
 // long rays (render_bwd.hip) as its carry-only pass
 int diffus::launch_fwd(const Args &A, int sampler, int layout, hipStream_t st)
 {
-    const bool f32 = !A.src_f64 && !A.dir_f64;
     return dispatch_sl(sampler, layout, [&](auto S_, auto L_) {
         constexpr int SM = decltype(S_)::value, LY = decltype(L_)::value;
-        if (A.N1 > DIFFUS_MAX_SAMPLES) return f32 ? launch_fwd_seg<SM, LY, 0>(A, st) : launch_fwd_seg<SM, LY, 1>(A, st);
-        return f32 ? launch_fwd_t<SM, LY, 0>(A, st) : launch_fwd_t<SM, LY, 1>(A, st);
+        return dispatch_pm(A, [&](auto P_) {
+            constexpr int PM = decltype(P_)::value;
+            return A.N1 > DIFFUS_MAX_SAMPLES ? launch_fwd_seg<SM, LY, PM>(A, st) : launch_fwd_t<SM, LY, PM>(A, st);
+        });
     });
 }
 
@@ -537,8 +538,11 @@ int diffus::launch_fwd(const Args &A, int sampler, int layout, hipStream_t st)
 int diffus::launch_median(const Args &A, int sampler, int layout, hipStream_t st)
 {
     return dispatch_sl(sampler, layout, [&](auto S_, auto L_) {
-        hipLaunchKernelGGL((median_kernel<decltype(S_)::value, decltype(L_)::value>), dim3(A.P), dim3(kBlock),
-                           sizeof(float) * (size_t)A.R, st, A);
+        constexpr int SM = decltype(S_)::value, LY = decltype(L_)::value;
+        if (A.src_per_ray)
+            hipLaunchKernelGGL((median_kernel<SM, LY, true>), dim3(A.P), dim3(kBlock), sizeof(float) * (size_t)A.R, st, A);
+        else
+            hipLaunchKernelGGL((median_kernel<SM, LY, false>), dim3(A.P), dim3(kBlock), sizeof(float) * (size_t)A.R, st, A);
         return last_launch();
     });
 }
@@ -546,10 +550,9 @@ int diffus::launch_median(const Args &A, int sampler, int layout, hipStream_t st
 namespace {
 int launch_fwd_long_repair(const Args &A, int sampler, int layout, hipStream_t st)
 {
-    const bool f32 = !A.src_f64 && !A.dir_f64;
     return dispatch_sl(sampler, layout, [&](auto S_, auto L_) {
         constexpr int SM = decltype(S_)::value, LY = decltype(L_)::value;
-        return f32 ? launch_fwd_long_repair_t<SM, LY, 0>(A, st) : launch_fwd_long_repair_t<SM, LY, 1>(A, st);
+        return dispatch_pm(A, [&](auto P_) { return launch_fwd_long_repair_t<SM, LY, decltype(P_)::value>(A, st); });
     });
 }
 } // namespace
@@ -637,8 +640,11 @@ int diffus_trace_rays(const float *vol, int d0, int d1, int d2, int layout, cons
     if (nblk > 256u * 16u) nblk = 256u * 16u;
     hipStream_t st = (hipStream_t)stream;
     return dispatch_sl(sampler, layout, [&](auto S_, auto L_) {
-        hipLaunchKernelGGL((trace_rays_kernel<decltype(S_)::value, decltype(L_)::value>), dim3(nblk), dim3(kBlock), 0, st,
-                           A, imp, refl, (long long *)idx);
+        constexpr int SM = decltype(S_)::value, LY = decltype(L_)::value;
+        if (A.src_per_ray)
+            hipLaunchKernelGGL((trace_rays_kernel<SM, LY, true>), dim3(nblk), dim3(kBlock), 0, st, A, imp, refl, (long long *)idx);
+        else
+            hipLaunchKernelGGL((trace_rays_kernel<SM, LY, false>), dim3(nblk), dim3(kBlock), 0, st, A, imp, refl, (long long *)idx);
         return last_launch();
     });
 }

@@ -98,7 +98,7 @@ constexpr unsigned kRowPad = DIFFUS_SC_ROW_PAD; // planar tile: padding entries 
 // general 3-D path); true when the patch is done.
 template <int SAMPLER, int PM, int CAP>
 __device__ __forceinline__ bool scatter_patch_planar(const Args &A, double *tile, int (*s_box)[4], int *s_planar, int *s_live, const Pose &ps,
-                                                     const float *rows, unsigned row_off, bool ray_ok, int nbase, int tid)
+                                                     const float *rows, unsigned row_off, bool ray_ok, int nbase, int tid, float zfirst)
 {
     // rows: zbar at the block's first ray (block-uniform, a scalar base); row_off: this thread's ray and first step in
     // BYTES from there (32 bits: no 64-bit multiply per lane)
@@ -128,7 +128,11 @@ __device__ __forceinline__ bool scatter_patch_planar(const Args &A, double *tile
         for (int e = 0; e < CAP / 4 / kSB; ++e) t4[e * kSB + tid] = make_int4(0, 0, 0, 0);
         static_assert(CAP % (4 * kSB) == 0, "tile clear assumes whole int4 passes");
     }
-    const bool ray_planar = (PM == 0 || ps.pmode != 2) ? (ps.df[2] == 0.f) : (ps.dd[2] == 0.0);
+    bool ray_planar = ((PM & 1) == 0 || ps.pmode != 2) ? (ps.df[2] == 0.f) : (ps.dd[2] == 0.0);
+    // Per-ray sources (PM bit 1): a ray with a zero dim-2 direction stays at the dim-2 coordinate of ITS source (p2 of every
+    // sample is float(source[2]), whatever the dtypes).  The patch's single dim-2 cell below needs that coordinate to be the
+    // same for every ray of the block: each ray compares its own with the block's first ray's (zfirst, block-uniform).
+    if constexpr ((PM & 2) != 0) ray_planar = ray_planar && ps.sf[2] == zfirst;
     const bool wave_planar = __ballot(ray_planar) == ~0ull;
     // ---- cells along dim 0 and dim 1 (the pose only: worked out while the loads are in flight)
     int x0[kSPT], x1[kSPT], y0[kSPT], y1[kSPT];
@@ -205,7 +209,7 @@ __device__ __forceinline__ bool scatter_patch_planar(const Args &A, double *tile
         nsub = 2;
         if (box_of(0, kSW / 2, t0, t1, t2, t3) > kCapD || box_of(kSW / 2, kSW / 2, t0, t1, t2, t3) > kCapD) nsub = 4;
     }
-    // the patch's dim-2 cell: the same in every thread (p2 = source[2] for every sample)
+    // the patch's dim-2 cell: the same in every thread (p2 = source[2] for every sample; per-ray sources: checked above)
     int iz0, iz1;
     float tz;
     {
@@ -940,7 +944,7 @@ __global__ __launch_bounds__(kSB, SLAB ? DIFFUS_SLAB_MIN_BLOCKS : DIFFUS_SC_MIN_
     // step group off blockIdx.y instead of dividing a linear index (uniform integer divisions are ~20 instructions each,
     // and every instruction of this kernel costs the same: fact 23).
     if (has_finish && blockIdx.y == 0) {
-        if (blockIdx.x < (unsigned)A.P) pose_finish_block<SAMPLER, LAYOUT, false>(A, (int)blockIdx.x, reinterpret_cast<float *>(tile));
+        if (blockIdx.x < (unsigned)A.P) pose_finish_block<SAMPLER, LAYOUT, false, (PM & 2) != 0>(A, (int)blockIdx.x, reinterpret_cast<float *>(tile));
         return;
     }
     // block -> (row, pose, ray group) with the row SLOWEST, and the row -> step group mapping of decode() below: the blocks
@@ -1012,7 +1016,10 @@ __global__ __launch_bounds__(kSB, SLAB ? DIFFUS_SLAB_MIN_BLOCKS : DIFFUS_SC_MIN_
             try_planar = __builtin_amdgcn_readfirstlane((int)(dfl[2] == 0.f)) != 0;
         }
         if (try_planar) {
-        if (scatter_patch_planar<SAMPLER, PM, CAP>(A, reinterpret_cast<double *>(tile), s_box, s_planar, &s_live, ps, A.zbar + w0 * A.N1, row_off, ray_ok, nbase, tid)) return;
+        float zfirst = 0.f; // per-ray sources: dim 2 of the block's first ray's source (a scalar load)
+        if constexpr ((PM & 2) != 0)
+            zfirst = ((PM & 1) && A.src_f64) ? (float)((const double *)A.src)[w0 * 3 + 2] : ((const float *)A.src)[w0 * 3 + 2];
+        if (scatter_patch_planar<SAMPLER, PM, CAP>(A, reinterpret_cast<double *>(tile), s_box, s_planar, &s_live, ps, A.zbar + w0 * A.N1, row_off, ray_ok, nbase, tid, zfirst)) return;
 #ifdef DIFFUS_SC_PLANAR_ONLY // timing probe: the general path compiled out (register budget of the planar path alone)
         return;
 #endif
@@ -1277,27 +1284,26 @@ int launch_scatter(const Args &A, int sampler, int layout, hipStream_t st)
     const int fin = A.finish_in_scatter ? 1 : 0;
     // x padded to a multiple of 8 (at most 7 idle blocks per row): see the XCD note in the kernel's decode()
     const dim3 grid((unsigned)((((long)A.P * rgs + 7) / 8) * 8), (unsigned)(sgs + fin)); // sgs <= 2048 (DIFFUS_MAX_SAMPLES * SEGMENTS / patch steps)
-    const bool f32 = !A.src_f64 && !A.dir_f64;
     const int glayout = layout == DIFFUS_PAIRED ? DIFFUS_BRICKED : layout; // the scatter only sees the gradient
     return dispatch_sl(sampler, glayout, [&](auto S_, auto L_) {
         constexpr int SM = decltype(S_)::value, LY = (decltype(L_)::value == DIFFUS_PAIRED) ? DIFFUS_BRICKED : decltype(L_)::value;
         // Fans the caller knows to be planar in dim 2 (DIFFUS_FANS_PLANAR), and canonical gradients: the 24 KiB tile at 6 blocks
         // per CU.  Otherwise the launch that also carries the slab path (36 KiB, 4 blocks per CU): planar patches in it take
         // the same planar path, ~10 % slower for the two blocks per CU it gives up; oblique ones no longer fall off a cliff.
+        // Per-ray sources: no slab path (its plane goes through ONE source); oblique patches take the 3-D tile.
         if constexpr (LY == DIFFUS_BRICKED) {
-            if (!A.fans_planar) {
-                if (f32)
+            if (!A.fans_planar && !A.src_per_ray) {
+                if (!A.src_f64 && !A.dir_f64)
                     hipLaunchKernelGGL((scatter_patch_kernel<SM, LY, 0, true>), grid, dim3(kSB), 0, st, A, rgs, fin, sgs, sg_mul);
                 else
                     hipLaunchKernelGGL((scatter_patch_kernel<SM, LY, 1, true>), grid, dim3(kSB), 0, st, A, rgs, fin, sgs, sg_mul);
                 return last_launch();
             }
         }
-        if (f32)
-            hipLaunchKernelGGL((scatter_patch_kernel<SM, LY, 0>), grid, dim3(kSB), 0, st, A, rgs, fin, sgs, sg_mul);
-        else
-            hipLaunchKernelGGL((scatter_patch_kernel<SM, LY, 1>), grid, dim3(kSB), 0, st, A, rgs, fin, sgs, sg_mul);
-        return last_launch();
+        return dispatch_pm(A, [&](auto P_) {
+            hipLaunchKernelGGL((scatter_patch_kernel<SM, LY, decltype(P_)::value>), grid, dim3(kSB), 0, st, A, rgs, fin, sgs, sg_mul);
+            return last_launch();
+        });
     });
 }
 } // namespace diffus

@@ -73,7 +73,7 @@ __global__ __launch_bounds__(kBlock) void sample_points_bwd_kernel(const float *
 // across a chunk edge from the previous chunk's last lane and one extra sample of lane 63.
 //   gz_k = gimp[k] + g * d r_{k-1} / d Z_k + g * d r_k / d Z_k   -> gvol (cell of sample k)
 //   trilinear: gsrc_part[ray] = sum_k gz_k grad v(p_k),  gdirs[ray] = sum_k k gz_k grad v(p_k)  (wave sums, fixed order)
-template <int SAMPLER, int LAYOUT>
+template <int SAMPLER, int LAYOUT, bool PR>
 __global__ __launch_bounds__(kBlock) void trace_rays_bwd_kernel(Args A, const float *__restrict__ gimp,
                                                                 const float *__restrict__ grefl, float *__restrict__ gvol,
                                                                 float *__restrict__ gsrc_part, float *__restrict__ gdirs)
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(kBlock) void trace_rays_bwd_kernel(Args A, const fl
     if (w >= (long)A.P * A.R) return; // (wave-uniform)
     const int lane = threadIdx.x & 63, S = A.S;
     Pose ps;
-    load_pose(ps, A.src, A.src_f64, A.dirs, A.dir_f64, w / A.R, w);
+    load_pose<PR ? 3 : 1>(ps, A.src, A.src_f64, A.dirs, A.dir_f64, w / A.R, w);
     float zlast = 0.f;                // Z of the previous chunk's last sample
     float gs[3] = {0.f, 0.f, 0.f}, gd[3] = {0.f, 0.f, 0.f};
     for (int base = 0; base < S; base += kWave) {
@@ -267,23 +267,29 @@ int diffus_trace_rays_bwd(const float *vol, int d0, int d1, int d2, int layout, 
     int rc = check_common(vol, d0, d1, d2, src, src_dtype, dirs, dirs_dtype, P, R, S, 0, sampler, layout, false);
     if (rc) return rc;
     const bool tri = sampler == DIFFUS_TRILINEAR;
-    if (tri && gsrc && (!workspace || workspace_bytes < diffus_trace_rays_bwd_workspace_bytes(P, R))) return DIFFUS_EWORKSPACE;
+    const bool per_ray = (src_dtype & DIFFUS_SRC_PER_RAY) != 0; // gsrc (P,R,3): the kernel's per-ray sums ARE the result
+    if (tri && gsrc && !per_ray && (!workspace || workspace_bytes < diffus_trace_rays_bwd_workspace_bytes(P, R))) return DIFFUS_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const bool grad = gimp || (grefl && S > 1);
     // nearest (or no incoming gradient): no pose gradient -- zeros, as diffus_render_bwd writes
-    if (gsrc && (!tri || !grad) && hipMemsetAsync(gsrc, 0, sizeof(float) * 3 * (size_t)P, st) != hipSuccess) return DIFFUS_ELAUNCH;
+    if (gsrc && (!tri || !grad) && hipMemsetAsync(gsrc, 0, sizeof(float) * 3 * (size_t)P * (per_ray ? R : 1), st) != hipSuccess) return DIFFUS_ELAUNCH;
     if (gdirs && (!tri || !grad) && hipMemsetAsync(gdirs, 0, sizeof(float) * 3 * (size_t)P * R, st) != hipSuccess) return DIFFUS_ELAUNCH;
     if (!grad || !(gvol || (tri && (gsrc || gdirs)))) return DIFFUS_OK;
     const Workspace none{}; // the kernel reads the volume and the poses of Args only: no render workspace behind it
     Args A = make_args(vol, d0, d1, d2, layout, src, src_dtype, dirs, dirs_dtype, P, R, S, 0, 0.f, none);
-    float *part = (tri && gsrc) ? (float *)workspace : nullptr;
+    float *part = (tri && gsrc) ? (per_ray ? gsrc : (float *)workspace) : nullptr;
     const unsigned nblk = (unsigned)(((long)P * R + kWavesPerBlock - 1) / kWavesPerBlock);
     rc = dispatch_sl(sampler, layout, [&](auto S_, auto L_) {
-        hipLaunchKernelGGL((trace_rays_bwd_kernel<decltype(S_)::value, decltype(L_)::value>), dim3(nblk), dim3(kBlock), 0, st,
-                           A, gimp, (S > 1) ? grefl : nullptr, gvol, part, tri ? gdirs : nullptr);
+        constexpr int SM = decltype(S_)::value, LY = decltype(L_)::value;
+        if (per_ray)
+            hipLaunchKernelGGL((trace_rays_bwd_kernel<SM, LY, true>), dim3(nblk), dim3(kBlock), 0, st,
+                               A, gimp, (S > 1) ? grefl : nullptr, gvol, part, tri ? gdirs : nullptr);
+        else
+            hipLaunchKernelGGL((trace_rays_bwd_kernel<SM, LY, false>), dim3(nblk), dim3(kBlock), 0, st,
+                               A, gimp, (S > 1) ? grefl : nullptr, gvol, part, tri ? gdirs : nullptr);
         return last_launch();
     });
-    if (rc || !part) return rc;
+    if (rc || !part || per_ray) return rc;
     hipLaunchKernelGGL(pose_sum_kernel, dim3((unsigned)P), dim3(kBlock), 0, st, part, R, gsrc);
     return last_launch();
 }

@@ -389,8 +389,22 @@ def _fans_planar(directions: torch.Tensor):
     return val
 
 
+def _sources_level(sources: torch.Tensor):
+    """Per-ray sources (P,R,3): whether every pose's origins share one dim-2 coordinate -- with directions that do not move
+    along dim 2, the array then lies in one slice and the planar-fan hint holds.  Same rules as _fans_planar: host tensors
+    are looked at, a device tensor that is not being optimised costs one readback, one that requires grad is unknown
+    (None) unless ArrayPose marked it."""
+    if getattr(sources, "_diffus_planar", False):
+        return True
+    if sources.is_cuda and (sources.requires_grad or sources.grad_fn is not None):
+        return None
+    s = sources.detach()[..., 2]
+    return bool((s == s[..., :1]).all())
+
+
 class _Problem:
-    """Validated, device-resident arguments of one (batched) call."""
+    """Validated, device-resident arguments of one (batched) call.  `sources` (P,3) or (3,): one apex per pose;
+    (P,R,3): one origin per ray (DIFFUS_SRC_PER_RAY) -- a 3-D `sources` is the only thing that selects that form."""
 
     def __init__(self, volume, sources, directions, S, start, alpha, sampler, layout="auto", shape=None):
         if layout not in _LAYOUTS + ("prebricked",):
@@ -410,21 +424,32 @@ class _Problem:
         self._layout_req, self._vol_src = layout, volume
         self._common = None
         sd, dd = _pose_dtype(sources), _pose_dtype(directions)
+        self.per_ray = sources.dim() == 3
+        if self.per_ray and (sources.shape[-1] != 3 or directions.shape[-1] != 3 or directions.dim() not in (2, 3)
+                             or directions.shape[-2] != sources.shape[1]
+                             or (directions.dim() == 3 and directions.shape[0] != sources.shape[0])):
+            raise ValueError(f"per-ray sources (P,R,3) need directions (R,3) or (P,R,3) with the same R; got sources "
+                             f"{tuple(sources.shape)}, directions {tuple(directions.shape)}")
+
+        def planar_hint(srcs, dirs):
+            p = _fans_planar(dirs)
+            return (p and _sources_level(srcs)) if self.per_ray else p
+
         if not sources.is_cuda and not directions.is_cuda:       # host poses: one packed, asynchronous upload ...
             hit = _host_pose_lookup(self.dev, sources, directions)
             if hit is not None:                                  # ... once per (tensor, version): a notebook renders the same fan again
                 sources, directions, self.planar = hit
             else:
-                self.planar = _fans_planar(directions)
+                self.planar = planar_hint(sources, directions)
                 with _Scope(self.dev):
                     up = _upload_small(self.dev, [(sources, sd), (directions, dd)])
                 if up is not None:
                     _host_pose_store(self.dev, sources, directions, up[0], up[1], self.planar)
                     sources, directions = up
         else:
-            self.planar = _fans_planar(directions)
+            self.planar = planar_hint(sources, directions)
         self.src = _as(sources, self.dev, sd)
-        if self.src.dim() != 2 or self.src.shape[1] != 3:
+        if not self.per_ray and (self.src.dim() != 2 or self.src.shape[1] != 3):
             self.src = self.src.reshape(-1, 3)
             if not self.src.is_contiguous():
                 self.src = self.src.contiguous()
@@ -441,7 +466,7 @@ class _Problem:
         self.S, self.start, self.alpha = int(S), int(start), float(alpha)
         self.N1 = self.S - self.start
         self.sampler = _SAMPLERS[sampler]
-        self.src_dt = _lib.DIFFUS_F64 if sd == torch.float64 else _lib.DIFFUS_F32
+        self.src_dt = (_lib.DIFFUS_F64 if sd == torch.float64 else _lib.DIFFUS_F32) | (_lib.SRC_PER_RAY if self.per_ray else 0)
         self.dir_dt = _lib.DIFFUS_F64 if dd == torch.float64 else _lib.DIFFUS_F32
         if self.bricked is None:
             self.bricked, self.layout = _converted_copy(self.vol, volume, layout, self.P * self.R * self.N1)
@@ -577,7 +602,7 @@ class _RenderFn(torch.autograd.Function):
                 else:       # sparse: persistent all-zero scratch + touched flags, flushed below
                     gvol, touched = _gradbuf(pb.dev, pb.shape)
                     sparse = True
-            gsrc = torch.empty((pb.P, 3), dtype=torch.float32, device=pb.dev) if need_s else None
+            gsrc = torch.empty(pb.src.shape, dtype=torch.float32, device=pb.dev) if need_s else None
             gdirs = torch.empty((pb.P, pb.R, 3), dtype=torch.float32, device=pb.dev) if need_d else None
             ws = pb.workspace()
             rc = lib.diffus_render_bwd(*common, _ptr(g), _ptr(gvol), _ptr(touched), _ptr(gsrc), _ptr(gdirs),
@@ -597,8 +622,9 @@ def render_poses(volume, sources, directions, num_samples, attenuation_coeff, st
                  return_indices=False, layout="auto", _squeeze_pose=False):
     """Batched hot path: P poses in one launch.
 
-    volume (d0,d1,d2) tensor or BrickedVolume; sources (P,3) or (3,); directions (P,R,3) or (R,3) shared.
-    -> frame (P,R,num_samples-start) float32 [, idx (3,P,R,N1) int64].
+    volume (d0,d1,d2) tensor or BrickedVolume; sources (P,3) or (3,): one apex per pose (sector fans), or (P,R,3): one
+    origin per ray (linear and convex arrays, see diffus_amd.probes); directions (P,R,3) or (R,3) shared.
+    -> frame (P,R,num_samples-start) float32 [, idx (3,P,R,N1) int64].  d/dsources has the shape of `sources`.
     Differentiable in volume (both samplers) and in sources/directions (trilinear).
     """
     if sampler not in _SAMPLERS:
@@ -665,7 +691,7 @@ class _TraceFn(torch.autograd.Function):
             gi = _as(gimp, pb.dev, torch.float32) if gimp is not None and gimp.numel() else None
             gr = _as(grefl, pb.dev, torch.float32) if grefl is not None and grefl.numel() else None
             gvol = torch.zeros(pb.shape, dtype=torch.float32, device=pb.dev) if need_v else None
-            gsrc = torch.empty((pb.P, 3), dtype=torch.float32, device=pb.dev) if need_s else None
+            gsrc = torch.empty(pb.src.shape, dtype=torch.float32, device=pb.dev) if need_s else None
             gdirs = torch.empty((pb.P, pb.R, 3), dtype=torch.float32, device=pb.dev) if need_d else None
             nws = lib.diffus_trace_rays_bwd_workspace_bytes(pb.P, pb.R) if need_s else 0
             ws = torch.empty(nws, dtype=torch.uint8, device=pb.dev) if nws else None
@@ -681,7 +707,8 @@ class _TraceFn(torch.autograd.Function):
 def trace_rays(volume, sources, directions, num_samples, sampler="nearest", want=("imp", "refl", "idx"),
                layout="auto"):
     """Stage 1 alone (diffus_trace_rays): -> dict with imp (P,R,S), refl (P,R,S-1), idx (3,P,R,S) (None where not in
-    `want`).  Differentiable in volume (both samplers) and in sources/directions (trilinear; nearest gives them zeros,
+    `want`).  `sources` as in render_poses: (P,3) / (3,) one apex per pose, (P,R,3) one origin per ray.
+    Differentiable in volume (both samplers) and in sources/directions (trilinear; nearest gives them zeros,
     as render_poses does) through diffus_trace_rays_bwd."""
     if not _wants_grad(volume, sources, directions):
         pb = _Problem(volume, sources, directions, num_samples, 0, 0.0, sampler, layout)

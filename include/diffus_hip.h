@@ -50,6 +50,13 @@ extern "C" {
 #define DIFFUS_F32 0
 #define DIFFUS_F64 1
 #define DIFFUS_I64 2 /* diffus_splat_axes only: the int64 index planes plot_beam_frame returns */
+#define DIFFUS_SRC_PER_RAY 0x10 /* OR'ed into `src_dtype` of diffus_render_fwd, _render_bwd, _render_bwd_mse, _render_step_mse,
+                                   diffus_trace_rays and diffus_trace_rays_bwd: one beam ORIGIN per ray (linear and convex array
+                                   probes) instead of one apex per pose.  `src` is then (P,R,3) in the dtype of the low bits, and
+                                   `gsrc` (P,R,3) float32, overwritten, with no sum over rays.  The reference evaluates
+                                   source + k * dir for ONE source (src/renderer.py:119-124); the per-ray form applies that
+                                   formula, with the same roundings, row by row: ray r of pose p starts at src[p, r].  Any other
+                                   bit of `src_dtype`, or low bits other than DIFFUS_F32 / DIFFUS_F64, is DIFFUS_EINVAL. */
 
 /* sampler */
 #define DIFFUS_NEAREST   0 /* reference custom_nearest_sampler, src/renderer.py:741-759 */
@@ -169,6 +176,10 @@ int diffus_convert_volume_box(const float *vol, int d0, int d1, int d2, int layo
  *   frame  out (P,R,N1) float32   processed_output of the reference
  *   idx    out, nullable: (3,P,R,N1) int64 -- the x,y,z index planes the
  *          reference returns, already cropped to [:, start:]
+ * With DIFFUS_SRC_PER_RAY in src_dtype, src is (P,R,3): ray r of pose p starts at
+ * src[p, r] (linear / convex arrays); everything else, the start > 0 median over
+ * the pose's rays included, is unchanged.  The same holds for the three backward
+ * entry points below.
  */
 int diffus_render_fwd(const float *vol, int d0, int d1, int d2, int layout,
                       const void *src, int src_dtype,
@@ -193,7 +204,8 @@ int diffus_render_fwd(const float *vol, int d0, int d1, int d2, int layout,
  *          entry of every brick this call adds into is set to 1 (plain stores).
  *          Together with diffus_gradbuf_flush it makes the gradient SPARSE: keep
  *          gvol and gvol_touched all-zero between steps, flush after each backward.
- *   gsrc   nullable (P,3) float32, overwritten   (trilinear only, else zeros)
+ *   gsrc   nullable (P,3) float32, overwritten   (trilinear only, else zeros);
+ *          (P,R,3) with DIFFUS_SRC_PER_RAY in src_dtype
  *   gdirs  nullable (P,R,3) float32, overwritten (trilinear only, else zeros)
  * With start > 0 the median written into column 0 (reference :243-244) routes
  * its gradient to the ray that supplied the median, like torch.median.
@@ -277,6 +289,7 @@ int diffus_render_step_mse(const float *vol, int d0, int d1, int d2, int layout,
  *   imp   (P,R,S)   float32  sampled impedances (trace_ray's ray_values)
  *   refl  (P,R,S-1) float32  reflection coefficients (simulate_rays' R)
  *   idx   (3,P,R,S) int64    rounded, clamped voxel indices x,y,z
+ * DIFFUS_SRC_PER_RAY in src_dtype: src (P,R,3), one origin per ray.
  */
 int diffus_trace_rays(const float *vol, int d0, int d1, int d2, int layout,
                       const void *src, int src_dtype,
@@ -351,6 +364,7 @@ int diffus_sample_points_bwd(const float *vol, int d0, int d1, int d2, int layou
  *   and, trilinear only, to the pose: gsrc (P,3) = sum_{r,k} gz grad v(p_k), gdirs (P,R,3) = sum_k k gz grad v(p_k),
  *   float32 whatever src_dtype / dirs_dtype are.  Nearest writes zeros to gsrc / gdirs.  `workspace`:
  *   diffus_trace_rays_bwd_workspace_bytes(P, R) bytes, needed when gsrc is set (trilinear), else may be NULL.
+ *   DIFFUS_SRC_PER_RAY in src_dtype: src (P,R,3) and gsrc (P,R,3) = sum_k gz grad v(p_k) per ray; no workspace needed.
  */
 size_t diffus_trace_rays_bwd_workspace_bytes(int P, int R);
 int diffus_trace_rays_bwd(const float *vol, int d0, int d1, int d2, int layout, const void *src, int src_dtype,
