@@ -531,18 +531,12 @@ struct TriSample {
     float g0, g1, g2; // d v / d p (border rule applied)
 };
 
-// Trilinear sample at p; lerp order dim 2, dim 1, dim 0, each a + t*(b-a) --
-// the exact sequence of oracle/diffus_oracle.c orc_sample_trilinear.
-template <int LAYOUT, bool GRAD>
-__device__ __forceinline__ TriSample tri_sample(const float *__restrict__ vol, const Geom &G, float p0, float p1,
-                                                float p2)
+// The eight corners v<dim0><dim1><dim2> of a cell lerped in the order dim 2, dim 1, dim 0, each a + t*(b-a) as a separate
+// multiply and add -- the exact sequence of oracle/diffus_oracle.c orc_sample_trilinear.
+template <bool GRAD>
+__device__ __forceinline__ TriSample tri_lerp(float v000, float v001, float v010, float v011, float v100, float v101, float v110,
+                                              float v111, const Axis &a, const Axis &b, const Axis &c)
 {
-    Axis a = tri_axis(p0, G.d0), b = tri_axis(p1, G.d1), c = tri_axis(p2, G.d2);
-    float v000, v001, v010, v011, v100, v101, v110, v111;
-    load_zpair<LAYOUT>(vol, G, a.i0, b.i0, c, v000, v001);
-    load_zpair<LAYOUT>(vol, G, a.i0, b.i1, c, v010, v011);
-    load_zpair<LAYOUT>(vol, G, a.i1, b.i0, c, v100, v101);
-    load_zpair<LAYOUT>(vol, G, a.i1, b.i1, c, v110, v111);
     float e00 = v001 - v000, e01 = v011 - v010, e10 = v101 - v100, e11 = v111 - v110;
     float c00 = __fadd_rn(v000, __fmul_rn(c.t, e00)), c01 = __fadd_rn(v010, __fmul_rn(c.t, e01));
     float c10 = __fadd_rn(v100, __fmul_rn(c.t, e10)), c11 = __fadd_rn(v110, __fmul_rn(c.t, e11));
@@ -561,6 +555,29 @@ __device__ __forceinline__ TriSample tri_sample(const float *__restrict__ vol, c
         s.g0 = s.g1 = s.g2 = 0.f;
     }
     return s;
+}
+
+// Trilinear sample at p (tri_lerp)
+template <int LAYOUT, bool GRAD>
+__device__ __forceinline__ TriSample tri_sample(const float *__restrict__ vol, const Geom &G, float p0, float p1,
+                                                float p2)
+{
+    Axis a = tri_axis(p0, G.d0), b = tri_axis(p1, G.d1), c = tri_axis(p2, G.d2);
+    float v000, v001, v010, v011, v100, v101, v110, v111;
+    load_zpair<LAYOUT>(vol, G, a.i0, b.i0, c, v000, v001);
+    load_zpair<LAYOUT>(vol, G, a.i0, b.i1, c, v010, v011);
+    load_zpair<LAYOUT>(vol, G, a.i1, b.i0, c, v100, v101);
+    load_zpair<LAYOUT>(vol, G, a.i1, b.i1, c, v110, v111);
+    return tri_lerp<GRAD>(v000, v001, v010, v011, v100, v101, v110, v111, a, b, c);
+}
+
+// the impedance a sample at p reads with the stage-wise sampler: the nearest voxel or tri_sample
+template <int SAMPLER, int LAYOUT>
+__device__ __forceinline__ float sample_value(const float *__restrict__ vol, const Geom &G, const float (&p)[3])
+{
+    if (SAMPLER == DIFFUS_NEAREST)
+        return vol[vox_off<LAYOUT>(G, nearest_index(p[0], G.d0), nearest_index(p[1], G.d1), nearest_index(p[2], G.d2))];
+    return tri_sample<LAYOUT, false>(vol, G, p[0], p[1], p[2]).v;
 }
 
 // reflection coefficient (reference src/renderer.py:33): IEEE f32 sub, add, div -- used by the
@@ -856,13 +873,13 @@ __device__ __forceinline__ unsigned part_z(int z)
 
 // lerps of one trilinear sample from its 8 corner values (order 000,001,010,011,100,101,110,111 = dim0,dim1,dim2 bits).
 // Each lerp is ONE fused multiply-add, a + t (b - a) rounded once, and the lerps run dim 0 first, then dim 1, then dim 2
-// -- the oracle (oracle/diffus_oracle.c orc_sample_trilinear) does dim 2, dim 1, dim 0 with a separate multiply and add.
+// -- the oracle's sequence (tri_lerp) is dim 2, dim 1, dim 0 with a separate multiply and add.
 // Why: the corners arrive as two 16-byte rows (x0 and x1: y0z0, y0z1, y1z0, y1z1 -- a PAIRED record, or two canonical
 // pairs), i.e. in register PAIRS (z0, z1).  Dim 0 first keeps every operand in those pairs: the value is 3 v_pk_add +
 // 3 v_pk_fma + 2 scalar instructions, all three gradient components 9 more -- 17 against the 25 of the dim-2-first
 // order (which hipcc's SLP pass packed too, but behind ~20 register moves per sample: the fused kernels are
 // VALU-issue-bound).  Same trilinear polynomial, other rounding: <= 2e-7 relative from the oracle's sequence, inside the
-// 1e-5 frame tolerance; the stage-wise kernels (tri_sample) keep the oracle's exact sequence.
+// 1e-5 frame tolerance; the stage-wise kernels and the float64 repairs (tri_lerp) keep the oracle's exact sequence.
 typedef float V2f __attribute__((ext_vector_type(2)));
 // keep0/1/2: false where the border rule must zero that gradient component and the difference is not an exact 0 by
 // itself (tri_axis_g: only the low side of an axis whose upper neighbour is not addressed separately)
@@ -1169,6 +1186,40 @@ __device__ __forceinline__ DMat dmat_dpp_ident(const DMat &m) // the identity wh
     return DMat{dpp_mov_d<CTRL, ROW_MASK>(1.0, m.a), dpp_mov_d<CTRL, ROW_MASK>(0.0, m.b), dpp_mov_d<CTRL, ROW_MASK>(0.0, m.c),
                 dpp_mov_d<CTRL, ROW_MASK>(1.0, m.d)};
 }
+constexpr DMat kDMatIdentity{1.0, 0.0, 0.0, 1.0};
+// exclusive prefix product over the wave of each lane's local product L (lower lanes on the left); lane 0: identity
+__device__ __forceinline__ DMat dmat_wave_exclusive(DMat L, int lane)
+{
+#define DIFFUS_DMAT_SCAN_ROUND(CTRL, RMASK, HAS, RN)   \
+    {                                                  \
+        const DMat o = dmat_dpp_ident<CTRL, RMASK>(L); \
+        L = dmat_mul(o, L);                            \
+        if (RN) dmat_renorm(L);                        \
+    }
+    DIFFUS_SCAN_UP_ROUNDS(lane, DIFFUS_DMAT_SCAN_ROUND)
+#undef DIFFUS_DMAT_SCAN_ROUND
+    return dmat_dpp_ident<kDppWaveShr1, 0xf>(L);
+}
+// lane 63's matrix in every lane (v_readlane_b32)
+__device__ __forceinline__ DMat dmat_lane63(const DMat &m)
+{
+    auto bc = [](double x) {
+        const long long b = __double_as_longlong(x);
+        const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), kWave - 1), hi = __builtin_amdgcn_readlane((int)(b >> 32), kWave - 1);
+        return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+    };
+    return DMat{bc(m.a), bc(m.b), bc(m.c), bc(m.d)};
+}
+// (zc - zp) / (zp + zc) (reference :33): v_rcp_f64 and two Newton steps (to the last bit or two of a double: far below the float32
+// samples' own rounding) instead of the ~40 instructions of an IEEE division
+__device__ __forceinline__ double reflect_f64(double zp, double zc)
+{
+    const double den = zp + zc;
+    double x = __builtin_amdgcn_rcp(den);
+    x = x * __builtin_fma(-den, x, 2.0);
+    x = x * __builtin_fma(-den, x, 2.0);
+    return (zc - zp) * x;
+}
 // r[j]: the reflection coefficient entering sample n = lane * C + j (0 where there is none); e[j] gets echo_n (NaN -> 0,
 // reference :408).  carry: a product that precedes the whole wave (nullable).
 // last (nullable): gets the product up to and including the wave's last sample, every lane the same value (the carry of the next
@@ -1176,20 +1227,11 @@ __device__ __forceinline__ DMat dmat_dpp_ident(const DMat &m) // the identity wh
 template <int C, typename T>
 __device__ __forceinline__ void echo_chunk_f64(const T (&r)[C], int lane, float (&e)[C], const DMat *carry = nullptr, DMat *last = nullptr)
 {
-    DMat L{1.0, 0.0, 0.0, 1.0};
+    DMat L = kDMatIdentity;
 #pragma unroll
     for (int j = 0; j < C; ++j) L = dmat_step(L, (double)r[j]);
     dmat_renorm(L);
-#define DIFFUS_ROUND(CTRL, RMASK, HAS, RN)             \
-    {                                                  \
-        const DMat o = dmat_dpp_ident<CTRL, RMASK>(L); \
-        L = dmat_mul(o, L);                            \
-        if (RN) dmat_renorm(L);                        \
-    }
-    DIFFUS_SCAN_UP_ROUNDS(lane, DIFFUS_ROUND)
-#undef DIFFUS_ROUND
-    DMat Pm{dpp_mov_d<kDppWaveShr1, 0xf>(1.0, L.a), dpp_mov_d<kDppWaveShr1, 0xf>(0.0, L.b), dpp_mov_d<kDppWaveShr1, 0xf>(0.0, L.c),
-            dpp_mov_d<kDppWaveShr1, 0xf>(1.0, L.d)}; // exclusive prefix; lane 0: identity
+    DMat Pm = dmat_wave_exclusive(L, lane);
     if (carry) {
         Pm = dmat_mul(*carry, Pm);
         dmat_renorm(Pm);
@@ -1203,16 +1245,11 @@ __device__ __forceinline__ void echo_chunk_f64(const T (&r)[C], int lane, float 
     }
     if (last) {
         dmat_renorm(Pm);
-        auto bc = [](double x) {
-            const long long b = __double_as_longlong(x);
-            const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), kWave - 1), hi = __builtin_amdgcn_readlane((int)(b >> 32), kWave - 1);
-            return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-        };
-        *last = DMat{bc(Pm.a), bc(Pm.b), bc(Pm.c), bc(Pm.d)};
+        *last = dmat_lane63(Pm);
     }
 }
 // The float64 series of such a ray from its float32 impedance samples -- the samples taken AGAIN, with the stage-wise sampler
-// (tri_sample: the oracle's lerp sequence bit for bit, i.e. the reference's grid_sample / nearest gather): on these rays the
+// (sample_value: the oracle's lerp sequence bit for bit, i.e. the reference's grid_sample / nearest gather): on these rays the
 // last bit of a sample is worth as much as the scan's own noise (the fused gather's one-fma lerps differ from that sequence by
 // a rounding: 1e-4 of the ray's peak on pose 18 of config 3 with the scan already in float64).
 // A cold branch (__builtin_expect at the call sites: what the register allocator must move is moved around THIS block, not
@@ -1233,11 +1270,8 @@ __device__ __forceinline__ void echo_f64_rare(const Args &A, const Pose &ps, int
 #pragma unroll
     for (int j = 0; j < C; ++j) {
         const int k = A.start + seg0 + n0 + j; // (past the end of the ray: any point is clamped into the volume; masked below)
-        const float p0 = ray_point<PM>(ps, 0, k), p1 = ray_point<PM>(ps, 1, k), p2 = ray_point<PM>(ps, 2, k);
-        if (SAMPLER == DIFFUS_NEAREST)
-            z[j] = A.vol[vox_off<LAYOUT>(A.G, nearest_index(p0, A.G.d0), nearest_index(p1, A.G.d1), nearest_index(p2, A.G.d2))];
-        else
-            z[j] = tri_sample<LAYOUT, false>(A.vol, A.G, p0, p1, p2).v;
+        const float p[3] = {ray_point<PM>(ps, 0, k), ray_point<PM>(ps, 1, k), ray_point<PM>(ps, 2, k)};
+        z[j] = sample_value<SAMPLER, LAYOUT>(A.vol, A.G, p);
     }
     float zprev = lane_prev(z[C - 1], z[C - 1]);
     if (zcarry && lane == 0) zprev = *zcarry;
@@ -1252,31 +1286,15 @@ __device__ __forceinline__ void echo_f64_rare(const Args &A, const Pose &ps, int
 #pragma unroll
     for (int j = 0; j < C; ++j) {
         const int nl = n0 + j, n = seg0 + nl;
-        const double zp = (double)((j == 0) ? zprev : z[j == 0 ? 0 : j - 1]), zc = (double)z[j];
-        // (zc - zp) / (zp + zc): v_rcp_f64 and two Newton steps (to the last bit or two of a double: far below the float32 samples'
-        // own rounding) instead of the ~40 instructions of an IEEE division
-        const double den = zp + zc;
-        double x = __builtin_amdgcn_rcp(den);
-        x = x * __builtin_fma(-den, x, 2.0);
-        x = x * __builtin_fma(-den, x, 2.0);
-        double v = (zc - zp) * x;
+        double v = reflect_f64((double)((j == 0) ? zprev : z[j == 0 ? 0 : j - 1]), (double)z[j]);
         if (n == 1 && A.start > 0) v = (double)medv;
         r[j] = (n >= 1 && nl < segN) ? v : 0.0;
     }
-    DMat L{1.0, 0.0, 0.0, 1.0};
+    DMat L = kDMatIdentity;
 #pragma unroll
     for (int j = 0; j < C; ++j) L = dmat_step(L, r[j]);
     dmat_renorm(L);
-#define DIFFUS_ROUND(CTRL, RMASK, HAS, RN)             \
-    {                                                  \
-        const DMat o = dmat_dpp_ident<CTRL, RMASK>(L); \
-        L = dmat_mul(o, L);                            \
-        if (RN) dmat_renorm(L);                        \
-    }
-    DIFFUS_SCAN_UP_ROUNDS(lane, DIFFUS_ROUND)
-#undef DIFFUS_ROUND
-    DMat Pm{dpp_mov_d<kDppWaveShr1, 0xf>(1.0, L.a), dpp_mov_d<kDppWaveShr1, 0xf>(0.0, L.b), dpp_mov_d<kDppWaveShr1, 0xf>(0.0, L.c),
-            dpp_mov_d<kDppWaveShr1, 0xf>(1.0, L.d)}; // exclusive prefix; lane 0: identity
+    DMat Pm = dmat_wave_exclusive(L, lane);
     if (carry) {
         Pm = dmat_mul(*carry, Pm);
         dmat_renorm(Pm);
@@ -1291,12 +1309,7 @@ __device__ __forceinline__ void echo_f64_rare(const Args &A, const Pose &ps, int
     }
     if (last) { // (coefficients past segN are 0: identity steps -- lane 63 ends on the product up to the piece's last sample)
         dmat_renorm(Pm);
-        auto bc = [](double x) {
-            const long long b = __double_as_longlong(x);
-            const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), kWave - 1), hi = __builtin_amdgcn_readlane((int)(b >> 32), kWave - 1);
-            return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-        };
-        *last = DMat{bc(Pm.a), bc(Pm.b), bc(Pm.c), bc(Pm.d)};
+        *last = dmat_lane63(Pm);
     }
 }
 // wave-uniform: does any lane hold an echo that asks for the float64 evaluation?
@@ -1391,7 +1404,7 @@ __device__ __forceinline__ void for_each_corner(const Cell &c, float zb, F &&f)
 
 // ---- float64 repair of an ill-conditioned ray's frame row (one-pass step; called from pose_finish_block by ONE wave, all lanes
 // active).  The scan kernel flags rays with |echo| > kEchoRecheck; here the row is evaluated again as the float64 pipeline
-// from float32 samples taken with the ORACLE's lerp sequence (the stage-wise tri_sample), the frame row and the ray's loss term are overwritten.  The gradients keep the float32 scan's values (they carry
+// from float32 samples taken with the ORACLE's lerp sequence (tri_lerp), the frame row and the ray's loss term are overwritten.  The gradients keep the float32 scan's values (they carry
 // the same condition number whatever the arithmetic).  Off the critical path -- the per-pose blocks sit at the head of the
 // scatter launch.
 // It shares its kernels' register budget (the scatter's patch path: 80) and must not spill: scratch under every wave of a launch
@@ -1417,15 +1430,7 @@ __device__ __forceinline__ float sample_rt(const Args &A, const Pose &ps, int k)
     const unsigned o000 = vox_off_rt(lay, A.G, a.i0, b.i0, c.i0), o001 = vox_off_rt(lay, A.G, a.i0, b.i0, c.i1), o010 = vox_off_rt(lay, A.G, a.i0, b.i1, c.i0),
                    o011 = vox_off_rt(lay, A.G, a.i0, b.i1, c.i1), o100 = vox_off_rt(lay, A.G, a.i1, b.i0, c.i0), o101 = vox_off_rt(lay, A.G, a.i1, b.i0, c.i1),
                    o110 = vox_off_rt(lay, A.G, a.i1, b.i1, c.i0), o111 = vox_off_rt(lay, A.G, a.i1, b.i1, c.i1);
-    const float v000 = A.vol[o000], v001 = A.vol[o001], v010 = A.vol[o010], v011 = A.vol[o011];
-    const float v100 = A.vol[o100], v101 = A.vol[o101], v110 = A.vol[o110], v111 = A.vol[o111];
-    // tri_sample's sequence (= oracle/diffus_oracle.c orc_sample_trilinear): dim 2, dim 1, dim 0, a + t (b - a) as a separate multiply and add
-    const float e00 = v001 - v000, e01 = v011 - v010, e10 = v101 - v100, e11 = v111 - v110;
-    const float c00 = __fadd_rn(v000, __fmul_rn(c.t, e00)), c01 = __fadd_rn(v010, __fmul_rn(c.t, e01));
-    const float c10 = __fadd_rn(v100, __fmul_rn(c.t, e10)), c11 = __fadd_rn(v110, __fmul_rn(c.t, e11));
-    const float f0 = c01 - c00, f1 = c11 - c10;
-    const float q0 = __fadd_rn(c00, __fmul_rn(b.t, f0)), q1 = __fadd_rn(c10, __fmul_rn(b.t, f1));
-    return __fadd_rn(q0, __fmul_rn(a.t, q1 - q0));
+    return tri_lerp<false>(A.vol[o000], A.vol[o001], A.vol[o010], A.vol[o011], A.vol[o100], A.vol[o101], A.vol[o110], A.vol[o111], a, b, c).v;
 }
 template <int SAMPLER, int C, bool PR> // C samples per lane: 64 C >= N1 (8 for rays of up to 512 samples: half the serial chain of 16)
 __device__ __forceinline__ void repair_ray_f64(const Args &A, long pose, long w, float *zbuf)
@@ -1443,15 +1448,11 @@ __device__ __forceinline__ void repair_ray_f64(const Args &A, long pose, long w,
     }
     wave_lds_sync();
     auto coeff = [&](int n, double zp, double zc) -> double { // r entering sample n (reference :33, :243-244)
-        const double den = zp + zc;
-        double x = __builtin_amdgcn_rcp(den); // + two Newton steps: to the last bits of a double
-        x = x * __builtin_fma(-den, x, 2.0);
-        x = x * __builtin_fma(-den, x, 2.0);
-        double v = (zc - zp) * x;
+        double v = reflect_f64(zp, zc);
         if (n == 1 && A.start > 0) v = (double)medv;
         return (n >= 1 && n < N1) ? v : 0.0;
     };
-    DMat L{1.0, 0.0, 0.0, 1.0};
+    DMat L = kDMatIdentity;
     {
         double zp = (double)zbuf[max(n0 - 1, 0)];
 #pragma unroll 1
@@ -1462,16 +1463,7 @@ __device__ __forceinline__ void repair_ray_f64(const Args &A, long pose, long w,
             if ((j & 3) == 3) dmat_renorm(L);
         }
     }
-#define DIFFUS_ROUND(CTRL, RMASK, HAS, RN)             \
-    {                                                  \
-        const DMat o = dmat_dpp_ident<CTRL, RMASK>(L); \
-        L = dmat_mul(o, L);                            \
-        if (RN) dmat_renorm(L);                        \
-    }
-    DIFFUS_SCAN_UP_ROUNDS(lane, DIFFUS_ROUND)
-#undef DIFFUS_ROUND
-    DMat Pm{dpp_mov_d<kDppWaveShr1, 0xf>(1.0, L.a), dpp_mov_d<kDppWaveShr1, 0xf>(0.0, L.b), dpp_mov_d<kDppWaveShr1, 0xf>(0.0, L.c),
-            dpp_mov_d<kDppWaveShr1, 0xf>(1.0, L.d)}; // exclusive prefix; lane 0: identity
+    DMat Pm = dmat_wave_exclusive(L, lane);
     float ssq = 0.f;
     float *const frow = A.frame + w * N1;
     const float *const trow = A.target ? A.target + w * N1 : nullptr;

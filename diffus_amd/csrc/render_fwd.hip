@@ -124,17 +124,14 @@ __global__ __launch_bounds__(kBlock) void trace_rays_kernel(Args A, float *__res
         float zz[2];
         const int nq = (refl && k + 1 < A.S) ? 2 : 1;
         for (int q = 0; q < nq; ++q) {
-            float p0 = ray_point(ps, 0, k + q), p1 = ray_point(ps, 1, k + q), p2 = ray_point(ps, 2, k + q);
-            int i0 = nearest_index(p0, A.G.d0), i1 = nearest_index(p1, A.G.d1), i2 = nearest_index(p2, A.G.d2);
+            const float p[3] = {ray_point(ps, 0, k + q), ray_point(ps, 1, k + q), ray_point(ps, 2, k + q)};
+            const int i0 = nearest_index(p[0], A.G.d0), i1 = nearest_index(p[1], A.G.d1), i2 = nearest_index(p[2], A.G.d2);
             if (q == 0 && idx) {
                 idx[t] = i0;
                 idx[total + t] = i1;
                 idx[2 * total + t] = i2;
             }
-            if (SAMPLER == DIFFUS_NEAREST)
-                zz[q] = A.vol[vox_off<LAYOUT>(A.G, i0, i1, i2)];
-            else
-                zz[q] = tri_sample<LAYOUT, false>(A.vol, A.G, p0, p1, p2).v;
+            zz[q] = sample_value<SAMPLER, LAYOUT>(A.vol, A.G, p);
         }
         if (imp) imp[t] = zz[0];
         if (refl && k + 1 < A.S) refl[w * (A.S - 1) + k] = reflect(zz[0], zz[1]);
@@ -160,14 +157,14 @@ __global__ __launch_bounds__(kBlock) void echo_traces_kernel(const float *__rest
     // |r| <= 0.3 are ~33: beyond kCondBits the row takes the float64 path like an ill-conditioned echo does.
     constexpr float kCondBits = 20.f;
     float bits = 0.f;
+    auto coeff = [&](int n) { return (n >= 1 && n <= N) ? rin[w * N + n - 1] : 0.f; }; // r entering sample n (0 where there is none)
     for (int base = 0; base <= N; base += kWave * C) {
         const int n0 = base + lane * C;
         float r[C], e[C];
         float lb = 0.f;
 #pragma unroll
         for (int j = 0; j < C; ++j) {
-            int n = n0 + j;
-            r[j] = (n >= 1 && n <= N) ? rin[w * N + n - 1] : 0.f;
+            r[j] = coeff(n0 + j);
             lb -= __builtin_amdgcn_logf(fmaxf(fabsf(1.f - r[j] * r[j]), 0x1p-24f)); // (v_log_f32: log2; a NaN coefficient counts 24 bits)
         }
         bits += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_sum_to_lane63(lb)), kWave - 1));
@@ -185,16 +182,13 @@ __global__ __launch_bounds__(kBlock) void echo_traces_kernel(const float *__rest
         }
     }
     if (__builtin_expect(again, 0)) { // (wave-uniform) the whole row again, the running product carried from piece to piece in float64
-        DMat Kd{1.0, 0.0, 0.0, 1.0};
+        DMat Kd = kDMatIdentity;
 #pragma unroll 1
         for (int base = 0; base <= N; base += kWave * C) {
             const int n0 = base + lane * C;
             float r[C], e[C];
 #pragma unroll
-            for (int j = 0; j < C; ++j) {
-                int n = n0 + j;
-                r[j] = (n >= 1 && n <= N) ? rin[w * N + n - 1] : 0.f;
-            }
+            for (int j = 0; j < C; ++j) r[j] = coeff(n0 + j);
             DMat nextK;
             echo_chunk_f64<C>(r, lane, e, base ? &Kd : nullptr, &nextK);
             Kd = nextK;
@@ -353,14 +347,14 @@ __global__ __launch_bounds__(kBlock) void sample_points_kernel(const float *__re
                                                                long n, float *__restrict__ val, long long *__restrict__ idx)
 {
     for (long t = (long)blockIdx.x * kBlock + threadIdx.x; t < n; t += (long)gridDim.x * kBlock) {
-        const float p0 = pts[t * 3], p1 = pts[t * 3 + 1], p2 = pts[t * 3 + 2];
-        const int i0 = nearest_index(p0, G.d0), i1 = nearest_index(p1, G.d1), i2 = nearest_index(p2, G.d2);
+        const float p[3] = {pts[t * 3], pts[t * 3 + 1], pts[t * 3 + 2]};
+        const int i0 = nearest_index(p[0], G.d0), i1 = nearest_index(p[1], G.d1), i2 = nearest_index(p[2], G.d2);
         if (idx) {
             idx[t] = i0;
             idx[n + t] = i1;
             idx[2 * n + t] = i2;
         }
-        if (val) val[t] = (SAMPLER == DIFFUS_NEAREST) ? vol[vox_off<LAYOUT>(G, i0, i1, i2)] : tri_sample<LAYOUT, false>(vol, G, p0, p1, p2).v;
+        if (val) val[t] = sample_value<SAMPLER, LAYOUT>(vol, G, p);
     }
 }
 
@@ -380,7 +374,7 @@ __global__ __launch_bounds__(kBlock) void render_fwd_long_repair_kernel(Args A)
     Pose ps;
     load_pose<PM>(ps, A.src, A.src_f64, A.dirs, A.dir_f64, pose, w);
     const float medv = (A.start > 0) ? A.med[pose] : 0.f;
-    DMat K{1.0, 0.0, 0.0, 1.0};
+    DMat K = kDMatIdentity;
     float zc = 0.f;
 #pragma unroll 1
     for (int seg0 = 0; seg0 < A.N1; seg0 += kWave * C) {

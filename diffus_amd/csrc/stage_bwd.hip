@@ -21,15 +21,6 @@ __device__ __forceinline__ void scatter_cell(float *__restrict__ gvol, const Geo
     });
 }
 
-// the impedance a sample at p reads (trace_rays_kernel's value, bit for bit)
-template <int SAMPLER, int LAYOUT>
-__device__ __forceinline__ float sample_value(const float *__restrict__ vol, const Geom &G, const float (&p)[3])
-{
-    if (SAMPLER == DIFFUS_NEAREST)
-        return vol[vox_off<LAYOUT>(G, nearest_index(p[0], G.d0), nearest_index(p[1], G.d1), nearest_index(p[2], G.d2))];
-    return tri_sample<LAYOUT, false>(vol, G, p[0], p[1], p[2]).v;
-}
-
 // g * d r / d Z1 and g * d r / d Z2 of r = (Z2 - Z1) / (Z1 + Z2) (reference src/renderer.py:33), with the operands torch's
 // SubBackward, AddBackward and DivBackward use in float32: g / den to the numerator, -g * ((num / den) / den) to the
 // denominator.  So a sample pair with Z1 + Z2 = 0 gives the inf / NaN autograd gives through compute_reflection_coeff.
